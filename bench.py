@@ -15,7 +15,9 @@ torch.cuda.synchronize() on both sides and the MAX over ranks is used; `value` i
 backward, one SUM all-reduce of the flat gradient bucket, RMSprop) per GPU and step, every convolution / BatchNorm /
 warp of it on this package's own kernels (pointmvsnet_amd/train_ops.py).
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps and prints the contract fields (``metric``,
+``value``, ``unit``, ``higher_is_better``, ``dtype``, ``ms_per_step``, ...); ``--dump-outputs DIR`` also writes what the
+last timed step computed as .npy files.  With ``--full`` the line also carries
   roofline     - the dominant hand-written entry point of the path: achieved = algorithmic bytes (or flops) per
                  launch / average launch duration, measured with HIP events (torch.cuda.Event on the stream the
                  kernels are launched on) around every C-ABI call of an instrumented EAGER calibration pass BEFORE the
@@ -26,7 +28,9 @@ Rank 0 prints ONE JSON line.  Besides the contract fields it carries
   cpu_baseline - the reference's own CPU path when its staged package is present (oracle/_ref, kind "reference"),
                  else the CPU oracle (oracle/pointflow_oracle.py, kind "port"), timed on this host's cores on a
                  bounded sample of the same workload (rank 0, N=1 only);
-  kernels      - per-entry-point time split of the calibration pass (informational).
+  kernels      - per-entry-point time split of the calibration pass (informational);
+  and the PCIe-inclusive / one-lane figures, cfg 1's CPU baseline, the training step's block (cfg 2) and the reference
+  model.py route, each in the same process or in a child process after the headline.
 """
 import argparse
 import json
@@ -209,6 +213,13 @@ def parse_args():
     ap.add_argument("--cpu-repeats", type=int, default=3)
     ap.add_argument("--train-cpu-baseline", action="store_true",
                     help="cfg4 only: also time ONE oracle training step on the host (tens of seconds, ~15 GB of RAM)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure everything else: the per-entry-point calibration pass (roofline, "
+                         "kernels), the PCIe-inclusive and one-lane figures, the CPU baselines, the training step's block "
+                         "and the reference model.py route.  Off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / "
+                         "float64; at most 64 MB in all, larger arrays as a fixed seeded sample)")
     return ap.parse_args()
 
 
@@ -272,6 +283,36 @@ def to_device(data, dev):
     out["cam_params_list_host"] = data["cam_params_list"]
     out["mean_host"], out["std_host"] = data["mean"], data["std"]       # host copy: no D2H inside the step
     return out
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+    """Write ``{name: tensor}`` as ``out_dir/<name>.npy``: floating tensors keep float32 / float64, anything else becomes
+    float64.  When the whole set exceeds ``budget`` bytes, each array is cut to its share of the budget by a fixed sample
+    of its flat elements (seeded, sorted indices; the index vector goes beside it as ``<name>.sample_index.npy``), so two
+    runs with the same arguments write the same elements.  Returns {name: shape written}."""
+    import numpy as np
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu()
+        a = a.numpy() if a.dtype in (torch.float32, torch.float64) else a.to(torch.float64).numpy()
+        host[name] = np.ascontiguousarray(a)
+    total = sum(a.nbytes for a in host.values())
+    share = budget // (2 * max(1, len(host)))            # (room for the index vectors of sampled arrays)
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name in sorted(host):
+        a = host[name]
+        if total > budget and a.nbytes > share:
+            keep = max(1, share // (a.itemsize + 8))
+            idx = np.sort(np.random.RandomState(0).choice(a.size, size=keep, replace=False)).astype(np.float64)
+            np.save(os.path.join(out_dir, name + ".sample_index.npy"), idx)
+            a = a.reshape(-1)[idx.astype(np.int64)]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = list(a.shape)
+    return written
 
 
 def _reference_forward():
@@ -923,7 +964,7 @@ def run(args, emulate):
                 loss, _, preds = graphed_train(scenes[i % n_unique])
             else:
                 loss, _, preds = trainer(scenes[i % n_unique], img_scales, inter_scales)
-            return preds
+            return dict(preds, loss=loss)
     else:
         def eager_step(i):
             with torch.no_grad():
@@ -951,27 +992,30 @@ def run(args, emulate):
             return trainer(scenes[i % n_unique], img_scales, inter_scales)[2]
         return eager_step(i)
 
+    # (the calibration pass is --full only: a plain run has no roofline / kernels split)
+    split, by_tag, ncal = {}, {}, 0
     with pointflow.concurrency(cal_level):
         for i in range(min(max(args.warmup, 1), 3)):
             cal_step(i)
         torch.cuda.synchronize()
-        ncal = max(1, int(args.calibration_steps)) if not training else 3
-        cal = _lib.KernelTimer()
-        _lib.set_timer(cal)
-        # the per-entry-point clock wants launches that do not overlap: the late weight gradients go out on ONE stream for
-        # the calibration steps (the timed replay deals them to train_ops.WGRAD_STREAMS streams; two concurrent grids
-        # stretch each other's event pairs, which says nothing about either kernel)
-        from pointmvsnet_amd import train_ops as _train_ops
-        wg_streams, _train_ops.WGRAD_STREAMS = _train_ops.WGRAD_STREAMS, 1
-        try:
-            for i in range(ncal):
-                cal_step(i)
-        finally:
-            _train_ops.WGRAD_STREAMS = wg_streams
-        _lib.set_timer(None)
-    split = cal.summary()
+        if args.full:
+            ncal = max(1, int(args.calibration_steps)) if not training else 3
+            cal = _lib.KernelTimer()
+            _lib.set_timer(cal)
+            # the per-entry-point clock wants launches that do not overlap: the late weight gradients go out on ONE stream
+            # for the calibration steps (the timed replay deals them to train_ops.WGRAD_STREAMS streams; two concurrent
+            # grids stretch each other's event pairs, which says nothing about either kernel)
+            from pointmvsnet_amd import train_ops as _train_ops
+            wg_streams, _train_ops.WGRAD_STREAMS = _train_ops.WGRAD_STREAMS, 1
+            try:
+                for i in range(ncal):
+                    cal_step(i)
+            finally:
+                _train_ops.WGRAD_STREAMS = wg_streams
+            _lib.set_timer(None)
+            split = cal.summary()
+            by_tag = getattr(cal, "by_tag", {})
     dominant = max(split.items(), key=lambda kv: kv[1]["ms"])[0] if split else None
-    by_tag = getattr(cal, "by_tag", {})
 
     # ---- hipGraph capture of the whole forward (default) ------------------------------------------
     execution = "eager"
@@ -999,11 +1043,17 @@ def run(args, emulate):
 
     # ---- W untimed warm-up steps in the final execution mode, then the timed region: EXACTLY K steps ------------
     # (event records cannot live inside a replayed graph, so the per-kernel clock is the calibration pass above)
+    # run_step returns [(scene index in the step, outputs)] of its last `keep` scenes: with scene lanes, the outputs of the
+    # last scene of every lane stay intact in the lane's static tensors until its next submit (--dump-outputs writes them)
+    keep = min(sps, laned.lanes) if execution != "eager" else 1
+
     def run_step(k):
-        out = None
+        outs = []
         for j in range(sps):
             out = step(k * sps + j)
-        return out
+            if j >= sps - keep:
+                outs.append((j, out))
+        return outs
 
     for k in range(args.warmup):
         run_step(k)
@@ -1019,7 +1069,7 @@ def run(args, emulate):
     wall_t0 = time.time()
     t0 = time.perf_counter()
     for k in range(args.steps):
-        preds = run_step(args.warmup + k)
+        last = run_step(args.warmup + k)
     # wall time until the last step is ENQUEUED (diagnostic only).  Not the host's cost: a lane's pinned constant block is
     # refilled only after its previous upload has run, which queues behind the lane's previous replay, so the enqueue
     # loop is paced by the GPU (one replay queued per lane); the host's own share is ~0.1 ms of camera algebra + ~0.3 ms
@@ -1029,6 +1079,21 @@ def run(args, emulate):
     barrier()
     elapsed = time.perf_counter() - t0
     wall_t1 = time.time()
+    preds = last[-1][1]
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller: every output of its last scene (and of the scenes still intact in
+        # the other lanes, as scene<j>_<name>); the training step's loss, its parameters after RMSprop and its gradients
+        arrays = {}
+        for j, out in last:
+            for name, t in out.items():
+                if torch.is_tensor(t):
+                    arrays[name if j == sps - 1 else "scene%d_%s" % (j, name)] = t
+        if training:
+            arrays["parameters"] = trainer.optimizer.flat if hasattr(trainer.optimizer, "flat") else \
+                torch.cat([p.detach().reshape(-1) for p in trainer.bucket.params])
+            arrays["gradients"] = trainer.bucket.flat
+        dumped = dump_outputs(args.dump_outputs, arrays)
     allreduce_us = None
     if training and world > 1:                   # the step's one collective on its own: 2.8 MB SUM all-reduce over RCCL
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(22)]
@@ -1040,7 +1105,7 @@ def run(args, emulate):
         torch.cuda.synchronize()
         allreduce_us = statistics.median(ev[j].elapsed_time(ev[j + 1]) for j in range(1, 21)) * 1e3
     gap_probe = None
-    if execution != "eager" and os.environ.get("PF_BENCH_GAP"):      # diagnostic, outside the timed region
+    if args.full and execution != "eager" and os.environ.get("PF_BENCH_GAP"):      # diagnostic, outside the timed region
         probe = []
         for g in graphs:
             g.probe = probe
@@ -1068,7 +1133,7 @@ def run(args, emulate):
     # reference's loop pays per scene (test.py:67-71) -- and (b) on ONE scene lane (batch-1 latency mode: one chain in
     # flight, intra-forward forks at the process default)
     value_pcie, value_one_lane, extras_note = None, None, None
-    if execution != "eager" and not training and args.route == "fused" and not args.no_extras:
+    if args.full and execution != "eager" and not training and args.route == "fused" and not args.no_extras:
         try:
             n_extra = max(laned.lanes * 8, min(args.steps * sps, 256 if args.config in ("cfg1", "cfg2") else 32))
             hosted = []
@@ -1102,7 +1167,7 @@ def run(args, emulate):
                 del one
         except Exception as exc:                       # say so in the line; the headline is already measured
             extras_note = repr(exc)
-    with_train = args.config == "cfg2" and args.route == "fused" and not args.no_train_block
+    with_train = args.full and args.config == "cfg2" and args.route == "fused" and not args.no_train_block
     placement_by_rank = None
     if world > 1:
         gathered = [None] * world
@@ -1184,7 +1249,7 @@ def run(args, emulate):
             kernels[k]["hbm_traffic_bytes_per_launch"] = measured_traffic(k)
     # the gather path as a whole (north_star: "achieved HBM GB/s on the gather path"): SURVEY 8(d)'s algorithmic
     # bytes per depth map over the summed HIP-event time of the PointFlow entry points in the calibration pass
-    gather_ms = sum(v["ms"] for k, v in split.items() if k in GATHER_PATH) / float(ncal)
+    gather_ms = sum(v["ms"] for k, v in split.items() if k in GATHER_PATH) / float(ncal) if ncal else 0.0
     if roof is not None and args.config in GATHER_PATH_MB and gather_ms > 0:
         gb = GATHER_PATH_MB[args.config] / 1e3
         roof["gather_path"] = {"algorithmic_MB_per_depth_map": GATHER_PATH_MB[args.config],
@@ -1237,11 +1302,13 @@ def run(args, emulate):
         "gap_probe": gap_probe,
         "stage_timeline_us": stage_timeline,
         "roofline": roof,
-        "parity": parity_summary() if not training else None,
+        "parity": parity_summary() if (args.full and not training) else None,
         "kernels": kernels,
         "train": None,
+        "full": bool(args.full),
+        "dumped_outputs": dumped,
     }
-    if world == 1 and not args.no_cpu_baseline and (not training or args.train_cpu_baseline):
+    if args.full and world == 1 and not args.no_cpu_baseline and (not training or args.train_cpu_baseline):
         data_cpu, _, _ = synthetic.make_config(args.config, seed=my_scenes[0], train_intrinsics=training)
         result["cpu_baseline"] = cpu_baseline(net, data_cpu, img_scales, inter_scales, args.cpu_repeats,
                                               WORKLOAD_TEXT[args.config], train=training)
@@ -1258,7 +1325,7 @@ def run(args, emulate):
                 result["cpu_baseline_cfg1"] = {"error": repr(exc)}
     else:
         result["cpu_baseline"] = None
-    with_route = (args.config == "cfg2" and args.route == "fused" and world == 1 and not args.no_extras
+    with_route = (args.full and args.config == "cfg2" and args.route == "fused" and world == 1 and not args.no_extras
                   and os.path.isfile(STAGED_MODEL_PY))
     if with_train or with_route:
         # the headline line is COMPLETE and on stdout before any child process starts: whatever happens in there (a hang,

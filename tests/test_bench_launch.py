@@ -113,7 +113,8 @@ def test_bench_line_assembles_on_the_emulator():
     if torch.cuda.is_available():
         pytest.skip("the emulator is for machines without a GPU")
     p = subprocess.run([sys.executable, BENCH, "--config", "tiny", "--steps", "1", "--warmup", "1", "--scenes-per-step", "1",
-                        "--calibration-steps", "1"], env=_env(PF_EMULATE="1"), capture_output=True, text=True, timeout=1800)
+                        "--calibration-steps", "1", "--full"], env=_env(PF_EMULATE="1"), capture_output=True, text=True,
+                       timeout=1800)
     assert p.returncode == 0, p.stderr[-3000:]
     out = _last_json(p.stdout)
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -127,6 +128,45 @@ def test_bench_line_assembles_on_the_emulator():
     assert inst and {"layer", "launches", "avg_launch_us", "frac_of_f32_mfma_peak"} <= set(inst[0])
     assert any(r["layer"] == "64->64 3x3/1" for r in inst)
     assert roof["under_load"] is None or roof["under_load"]["worst"]["frac_mfma_peak"] < roof["under_load"]["best"]["frac_mfma_peak"]
+
+
+def test_plain_line_is_lean_and_dumps_the_last_steps_outputs_on_the_emulator(tmp_path):
+    """A plain run (no --full) sets up, warms up, times exactly --steps steps and prints ONE line with the contract fields;
+    nothing else is measured (no calibration pass, CPU baseline, train block or route).  --dump-outputs writes what the
+    last timed step returned, float32, one .npy per output."""
+    if torch.cuda.is_available():
+        pytest.skip("the emulator is for machines without a GPU")
+    import numpy as np
+    out_dir = str(tmp_path / "outputs")
+    p = subprocess.run([sys.executable, BENCH, "--config", "tiny", "--steps", "2", "--warmup", "1", "--scenes-per-step", "1",
+                        "--dump-outputs", out_dir], env=_env(PF_EMULATE="1"), capture_output=True, text=True, timeout=1800)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 2 and out["value"] > 0 and out["ms_per_step"] > 0 and out["dtype"] == "f32"
+    assert out["higher_is_better"] is True and out["unit"] == "depth-maps/s" and out["full"] is False
+    assert out["roofline"] is None and out["kernels"] == {} and out["cpu_baseline"] is None and out["train"] is None
+    assert "route_reference_model" not in out and "cpu_baseline_cfg1" not in out
+    names = sorted(f[:-4] for f in os.listdir(out_dir) if f.endswith(".npy"))
+    assert names == sorted(out["dumped_outputs"]) and {"coarse_depth_map", "flow1", "flow2"} <= set(names)
+    flow2 = np.load(os.path.join(out_dir, "flow2.npy"))
+    assert flow2.dtype == np.float32 and list(flow2.shape) == [1, 1, 32, 48] and np.isfinite(flow2).all()
+
+
+def test_dump_outputs_samples_a_fixed_subset_beyond_the_budget(tmp_path):
+    sys.path.insert(0, ROOT)
+    import bench
+    import numpy as np
+    big = torch.arange(4096, dtype=torch.float32).view(64, 64)
+    small = torch.tensor([1, 2, 3], dtype=torch.int64)
+    shapes = [bench.dump_outputs(str(tmp_path / d), {"big": big, "small": small}, budget=4096) for d in ("a", "b")]
+    assert shapes[0] == shapes[1] and shapes[0]["small"] == [3] and 0 < shapes[0]["big"][0] < 4096
+    a, b = (np.load(str(tmp_path / d / "big.npy")) for d in ("a", "b"))
+    idx = np.load(str(tmp_path / "a" / "big.sample_index.npy"))
+    assert np.array_equal(a, b) and np.array_equal(a, idx.astype(np.float32)) and (np.diff(idx) > 0).all()
+    assert np.load(str(tmp_path / "a" / "small.npy")).dtype == np.float64
+    assert sum(os.path.getsize(str(tmp_path / "a" / f)) for f in os.listdir(str(tmp_path / "a"))) <= 4096 + 4 * 128
 
 
 def test_experiments_past_the_childs_budget_are_skipped_by_name(monkeypatch):

@@ -8,6 +8,6 @@ echo "== $v"; env $v timeout 300 python tools/microbench_train_ops.py 2>&1 | gre
 done
 paste <(cut -c1-52 gpurun_out/mb_PF_X=0.log) <(cut -c34-46 gpurun_out/mb_PF_WGRAD_SWAP=0.log) <(cut -c34-46 gpurun_out/mb_PF_WGRAD_DBG=4.log) | head -20
 for i in 1 2; do for v in PF_X=0 PF_WGRAD_SWAP=0; do
-env $v timeout 300 python bench.py --config cfg4 --no-cpu-baseline 2>/dev/null | grep "^{" | tail -1 | python -c "
+env $v timeout 300 python bench.py --full --config cfg4 --no-cpu-baseline 2>/dev/null | grep "^{" | tail -1 | python -c "
 import json,sys; d=json.loads(sys.stdin.readline()); print('cfg4 $v', round(d['value'],1), round(d['ms_per_step'],3), d['roofline']['weight_gradients']['kernel_us_per_step'])"
 done; done
