@@ -501,6 +501,35 @@ int pf_eval_prob_filter_f32(const float* depth, const float* flow_conf, const fl
                             int iw, float flow_threshold, float init_threshold, float* dst, int flip_rows,
                             void* stream);
 
+/* ---- depth-map fusion: filtered depth maps of V views -> one point cloud (csrc/fusion.hip) ---------------------
+ * What reference tools/depthfusion.py:173-192 delegates to the external program fusibile.  The specification is this
+ * project's own (pointmvsnet_amd/fusion.py): pixel (x, y) has its centre at (x + 0.5, y + 0.5),
+ * no normal test.  All maps are (V, h, w) row-major, 0 = no depth; colours are (V, h, w, 3) bytes or NULL.
+ * The host composes the matrices in float64 and passes them as float32:
+ *   view_maps (V, PF_FUSE_VIEW_FLOATS): A = R^-1 K^-1 (3x3 row-major), C = -R^-1 t;  X = (A (x+.5, y+.5, 1)) d + C
+ *   pair_maps (V, V, PF_FUSE_PAIR_FLOATS), entry [i][j]: M = K_j R_j R_i^-1 K_i^-1 (3x3), T = K_j (t_j - R_j R_i^-1 t_i),
+ *             fb = K_j[0][0] |C_i - C_j|, 3 floats of padding;  q = (M (x+.5, y+.5, 1)) d + T
+ * pf_fuse_stage_a_f32: per pixel p of view i with depth_min < d < depth_max and every other view j in ascending order:
+ *   z = q.z, (xj, yj) = floor(q.xy / z); j is consistent iff z > 0, (xj, yj) is inside the map, d_j(xj, yj) is inside
+ *   (depth_min, depth_max) and |fb / z - fb / d_j| < disp_threshold.  count (V,h,w) = consistent views; match
+ *   (V, V-1, h, w) = yj * w + xj or -1 (slot = j, or j - 1 behind i); point (V,h,w,3) / colour_out (V,h,w,3) = mean of
+ *   the pixel's own back-projection / colour and those of its matches (count + 1 terms; colour rounded to nearest).
+ *   Pixels without depth: count 0, match -1, point 0.
+ * pf_fuse_mark: stage B for view `view`, to be called for view = 0 .. V-1 in order on one stream with `used` (V,h,w)
+ *   zeroed before the first call: emit[view][p] = (used[view][p] == 0 && count[view][p] >= num_consistent); an emitting
+ *   pixel sets used[j][match] = 1 for each of its matches.
+ * pf_fuse_compact_f32: rows of point / colour (n rows) whose emit byte is set -> out row rank[i] - 1, rank = the
+ *   inclusive prefix sum of emit (int64); `rows` = rank[n-1] bounds the output. */
+#define PF_FUSE_VIEW_FLOATS 12
+#define PF_FUSE_PAIR_FLOATS 16
+int pf_fuse_stage_a_f32(const float* depth, const unsigned char* colour, const float* view_maps, const float* pair_maps,
+                        int V, int h, int w, float disp_threshold, float depth_min, float depth_max, int* count,
+                        float* point, unsigned char* colour_out, int* match, void* stream);
+int pf_fuse_mark(const int* count, const int* match, unsigned char* used, unsigned char* emit, int V, int view, int h,
+                 int w, int num_consistent, void* stream);
+int pf_fuse_compact_f32(const unsigned char* emit, const int64_t* rank, const float* point, const unsigned char* colour,
+                        int64_t n, int64_t rows, float* out_point, unsigned char* out_colour, void* stream);
+
 
 /* ==== Row Z : the training step (BASELINE config 4; reference train.py:72-82) ======================================
  * Hand-written backward for the convolution -> BatchNorm(batch statistics) -> ReLU blocks of ImageConv, VolumeConv

@@ -93,3 +93,62 @@ def cam_dtu_text(cam):
 def write_cam_dtu(file, cam):
     with open(file, "w") as f:
         f.write(cam_dtu_text(cam))
+
+
+def write_ply(file, points, colors=None):
+    """Binary little-endian PLY of a point cloud: ``x y z`` float32 per vertex, then ``red green blue`` uchar when
+    ``colors`` (N, 3) is given -- the vertex layout fusibile's final3d_model.ply carries, minus the normals."""
+    points = np.ascontiguousarray(points, dtype="<f4")
+    if points.ndim != 2 or points.shape[1] != 3:
+        raise Exception("Points must have N x 3 dimensions.")
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    header = "ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+    if colors is not None:
+        colors = np.asarray(colors)
+        if colors.shape != points.shape or colors.dtype != np.uint8:
+            raise Exception("Colors must be uint8 with the shape of the points.")
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+        header += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+    vertex = np.empty(points.shape[0], dtype=np.dtype(fields))
+    for c, n in enumerate("xyz"):
+        vertex[n] = points[:, c]
+    if colors is not None:
+        for c, n in enumerate(("red", "green", "blue")):
+            vertex[n] = colors[:, c]
+    with open(file, "wb") as f:
+        f.write((header % points.shape[0] + "end_header\n").encode("ascii"))
+        f.write(vertex.tobytes())
+
+
+def load_ply(file):
+    """(points (N, 3) float32, colors (N, 3) uint8 or None) of a PLY file as ``write_ply`` writes it."""
+    with open(file, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise Exception("Not a PLY file.")
+        count, props = None, []
+        while True:
+            line = f.readline()
+            if not line:
+                raise Exception("Malformed PLY header.")
+            words = line.decode("ascii").split()
+            if words == ["end_header"]:
+                break
+            if words[0] == "format" and words[1:] != ["binary_little_endian", "1.0"]:
+                raise Exception("Only binary_little_endian 1.0 PLY files are read.")
+            if words[0] == "element":
+                if words[1] != "vertex" or count is not None:
+                    raise Exception("Only PLY files with one vertex element are read.")
+                count = int(words[2])
+            if words[0] == "property":
+                props.append((words[1], words[2]))
+        xyz = [("float", n) for n in "xyz"]
+        rgb = [("uchar", n) for n in ("red", "green", "blue")]
+        if count is None or props not in (xyz, xyz + rgb):
+            raise Exception("Only x y z float [red green blue uchar] vertices are read.")
+        dtype = np.dtype([(n, "<f4" if t == "float" else "u1") for t, n in props])
+        vertex = np.frombuffer(f.read(count * dtype.itemsize), dtype=dtype, count=count)
+    points = np.stack([vertex[n] for n in "xyz"], axis=1) if count else np.zeros((0, 3), np.float32)
+    if len(props) == 3:
+        return points, None
+    colors = np.stack([vertex[n] for n in ("red", "green", "blue")], axis=1) if count else np.zeros((0, 3), np.uint8)
+    return points, colors
