@@ -530,6 +530,26 @@ int pf_fuse_mark(const int* count, const int* match, unsigned char* used, unsign
 int pf_fuse_compact_f32(const unsigned char* emit, const int64_t* rank, const float* point, const unsigned char* colour,
                         int64_t n, int64_t rows, float* out_point, unsigned char* out_colour, void* stream);
 
+/* ---- image preprocessing from decoded uint8 views (csrc/preprocess.hip) -----------------------------------------
+ * What reference dataset.py:269-287 does on the host before it uploads float32: cv2.resize, crop_dtu_input and
+ * norm_image (utils/preprocess.py:6-11,56-85).  Specification: pointmvsnet_amd/utils/preprocess.py (the resize is this
+ * project's own statement of bilinear interpolation with half-pixel centres, not OpenCV's fixed-point kernel).
+ * pf_preprocess_resize_u8: src (V, h_src, w_src, 3) interleaved bytes, 16-byte aligned.  Output pixel (y, x) of the
+ *   (H, W) cropped image blends the source pixels (yi[y] | yi[y]+1, xi[x] | xi[x]+1) (the +1 clamped to the last
+ *   row / column) with the weights yw[y], xw[x] of the second one:
+ *   (1-wy)*((1-wx)*p00 + wx*p01) + wy*((1-wx)*p10 + wx*p11) in float32, rounded half-to-even to a byte -> ref
+ *   (V, H, W, 3).  The tables (the host composes them in float64, crop offset included) must be non-decreasing;
+ *   span >= the largest number of source columns xi[last] + 2 - xi[first] that one tile of PF_PREPROCESS_TILE_X
+ *   output columns samples.  sums (V, 3, 2) 64-bit integers receives, per view and channel, sum p and sum p*p over
+ *   ref (zeroed by the call; integer atomics: exact, the same bits whatever the order).
+ * pf_preprocess_standardise_f32: out (V, 3, H, W) planar = float32((p - mean) / (sqrt(var) + 1e-7)) evaluated in
+ *   float64 with mean = S1 / N, var = (N S2 - S1^2) / N^2 (population variance) from the integers of `sums`. */
+#define PF_PREPROCESS_TILE_X 256
+int pf_preprocess_resize_u8(const unsigned char* src, int V, int h_src, int w_src, const int* xi, const float* xw,
+                            const int* yi, const float* yw, int H, int W, int span, unsigned char* ref,
+                            unsigned long long* sums, void* stream);
+int pf_preprocess_standardise_f32(const unsigned char* ref, const unsigned long long* sums, int V, int H, int W,
+                                  float* out, void* stream);
 
 /* ==== Row Z : the training step (BASELINE config 4; reference train.py:72-82) ======================================
  * Hand-written backward for the convolution -> BatchNorm(batch statistics) -> ReLU blocks of ImageConv, VolumeConv
