@@ -530,6 +530,47 @@ int pf_fuse_mark(const int* count, const int* match, unsigned char* used, unsign
 int pf_fuse_compact_f32(const unsigned char* emit, const int64_t* rank, const float* point, const unsigned char* colour,
                         int64_t n, int64_t rows, float* out_point, unsigned char* out_colour, void* stream);
 
+/* ---- point-cloud evaluation: thinning and nearest distances between unordered clouds (csrc/cloud_eval.hip) -------
+ * DTU's accuracy / completeness step, which the reference does not have (a separate MATLAB program).  The specification
+ * is this project's own (pointmvsnet_amd/evaluation.py).  A cloud is searched through a sparse grid
+ * kept as a sorted array: cell = floor((p - origin) / edge) per axis in float32, clamped to [0, n - 1];
+ * key = cx << 42 | cy << 21 | cz.  The caller sorts the keys (ascending; any order inside a cell) and passes the sorted
+ * keys together with the points gathered into that order.
+ * pf_cloud_cell_keys_f32: keys (n) of points (n, 3).  nx, ny, nz <= PF_CLOUD_MAX_CELLS (so that float32 rounding moves a
+ *   cell coordinate by < 0.016 cells, the margin every bound below keeps); n <= PF_CLOUD_MAX_POINTS everywhere.
+ * pf_cloud_pack_f32: packed (n) 16-byte records (x, y, z, uint32 tag), 16-byte aligned: record i = point order[i]; tag =
+ *   order[i], or with `hashed` prio(order[i]): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16.
+ * pf_cloud_thin_round: one round of the greedy minimum-distance thinning in its parallel form on a grid whose edge is
+ *   >= 1.05 * min_dist; t = float32(min_dist)^2.  States (n bytes, sorted order): 0 undecided, 1 kept, 2 removed.  An
+ *   undecided point i looks at every j with tag(j) < tag(i) and dx*dx + dy*dy + dz*dz < t in state_in: state_out = removed
+ *   if one of them is kept, kept if all are removed, else undecided, and then *pending is set to 1 (the caller clears it
+ *   before the round and repeats with the buffers swapped while it is set).
+ * pf_cloud_nn_cells_f32: per query (nq, 3) the nearest target point among the cubes of radius 1, 3, .. <= rings cells
+ *   around the query's cell; done = 1 and dist = min(sqrt(min d^2), max_dist), index = that point's tag (-1 where dist ==
+ *   max_dist) once the best distance is <= (radius - 0.05) * edge or that reach covers max_dist; else done = 0 and
+ *   dist / index are left alone.
+ * pf_cloud_nn_wave_f32: the same result for the queries todo[0 .. ntodo) (indices into query) from the 27 cells around
+ *   the query on a grid with edge >= max_dist (the caller adds the rounding margin), one wavefront per query. */
+#define PF_CLOUD_MAX_CELLS 131072
+#define PF_CLOUD_MAX_POINTS 2000000000
+int pf_cloud_cell_keys_f32(const float* points, int64_t n, float ox, float oy, float oz, float edge, int nx, int ny, int nz,
+                           int64_t* keys, void* stream);
+int pf_cloud_pack_f32(const float* points, const int64_t* order, int64_t n, int hashed, void* packed, void* stream);
+int pf_cloud_thin_round(const void* packed, const int64_t* keys, int64_t n, int nx, int ny, int nz, float t,
+                        const unsigned char* state_in, unsigned char* state_out, int* pending, void* stream);
+int pf_cloud_nn_cells_f32(const float* query, int64_t nq, const void* packed, const int64_t* keys, int64_t nt, float ox,
+                          float oy, float oz, float edge, int nx, int ny, int nz, int rings, float max_dist, float* dist,
+                          int* index, unsigned char* done, void* stream);
+int pf_cloud_nn_wave_f32(const float* query, const int64_t* todo, int64_t ntodo, int64_t nq, const void* packed,
+                         const int64_t* keys, int64_t nt, float ox, float oy, float oz, float edge, int nx, int ny, int nz,
+                         float max_dist, float* dist, int* index, void* stream);
+/* The two DTU filters.  inside[i] = mask[idx] != 0 with idx = floor((p - bb_min) / res + 0.5) per axis (float32) when idx
+ * lies in the (X, Y, Z) row-major byte grid, else 0.  above[i] = ((a x + b y) + c z) + d > 0. */
+int pf_cloud_obs_mask_f32(const float* points, int64_t n, const unsigned char* mask, int X, int Y, int Z, float bx, float by,
+                          float bz, float res, unsigned char* inside, void* stream);
+int pf_cloud_above_plane_f32(const float* points, int64_t n, float a, float b, float c, float d, unsigned char* above,
+                             void* stream);
+
 /* ---- image preprocessing from decoded uint8 views (csrc/preprocess.hip) -----------------------------------------
  * What reference dataset.py:269-287 does on the host before it uploads float32: cv2.resize, crop_dtu_input and
  * norm_image (utils/preprocess.py:6-11,56-85).  Specification: pointmvsnet_amd/utils/preprocess.py (the resize is this

@@ -110,6 +110,13 @@ PROTOTYPES = {
     "pf_fuse_stage_a_f32": ([_vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp], _i),
     "pf_fuse_mark": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
     "pf_fuse_compact_f32": ([_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp], _i),
+    "pf_cloud_cell_keys_f32": ([_vp, _i64, _f, _f, _f, _f, _i, _i, _i, _vp, _vp], _i),
+    "pf_cloud_pack_f32": ([_vp, _vp, _i64, _i, _vp, _vp], _i),
+    "pf_cloud_thin_round": ([_vp, _vp, _i64, _i, _i, _i, _f, _vp, _vp, _vp, _vp], _i),
+    "pf_cloud_nn_cells_f32": ([_vp, _i64, _vp, _vp, _i64, _f, _f, _f, _f, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp], _i),
+    "pf_cloud_nn_wave_f32": ([_vp, _vp, _i64, _i64, _vp, _vp, _i64, _f, _f, _f, _f, _i, _i, _i, _f, _vp, _vp, _vp], _i),
+    "pf_cloud_obs_mask_f32": ([_vp, _i64, _vp, _i, _i, _i, _f, _f, _f, _f, _vp, _vp], _i),
+    "pf_cloud_above_plane_f32": ([_vp, _i64, _f, _f, _f, _f, _vp, _vp], _i),
     "pf_preprocess_resize_u8": ([_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp], _i),
     "pf_preprocess_standardise_f32": ([_vp, _vp, _i, _i, _i, _vp, _vp], _i),
     "pf_softargmin_prob_f32": ([_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp], _i),

@@ -104,10 +104,11 @@ int pf_eval_prob_filter_f32(const float* depth, const float* flow_conf, const fl
 }  // extern "C"
 
 // A build that is not hipcc's (no __HIP__: the host re-compilation of tests/hipemu, whose list of sources is fixed) gets
-// the next stage of the evaluation output, the fusion kernels, and the scene input (preprocess.hip) with this unit, so that
-// such a library exports the whole C ABI.  hipcc compiles fusion.hip and preprocess.hip as units of their own
-// (build.SOURCES) and never takes this branch.
+// the next stage of the evaluation output, the fusion kernels, the scene input (preprocess.hip) and the point-cloud
+// evaluation (cloud_eval.hip) with this unit, so that such a library exports the whole C ABI.  hipcc compiles fusion.hip,
+// preprocess.hip and cloud_eval.hip as units of their own (build.SOURCES) and never takes this branch.
 #if !defined(__HIP__)
 #include "fusion.hip"
 #include "preprocess.hip"
+#include "cloud_eval.hip"
 #endif

@@ -152,3 +152,75 @@ def load_ply(file):
         return points, None
     colors = np.stack([vertex[n] for n in ("red", "green", "blue")], axis=1) if count else np.zeros((0, 3), np.uint8)
     return points, colors
+
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "<i2", "int16": "<i2", "ushort": "<u2",
+              "uint16": "<u2", "int": "<i4", "int32": "<i4", "uint": "<u4", "uint32": "<u4", "float": "<f4",
+              "float32": "<f4", "double": "<f8", "float64": "<f8"}
+
+
+def load_ply_points(file):
+    """(N, 3) float32 ``x y z`` of a binary-little-endian PLY whose FIRST element is ``vertex`` with any scalar properties
+    (fusibile's clouds and DTU's ``stlNNN_total.ply`` carry normals and colours); later elements such as faces are ignored."""
+    with open(file, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise Exception("Not a PLY file.")
+        elements = []                                   # (name, count, [(type, name)])
+        while True:
+            line = f.readline()
+            if not line:
+                raise Exception("Malformed PLY header.")
+            words = line.decode("ascii").split()
+            if not words or words[0] in ("comment", "obj_info"):
+                continue
+            if words == ["end_header"]:
+                break
+            if words[0] == "format" and words[1:] != ["binary_little_endian", "1.0"]:
+                raise Exception("Only binary_little_endian 1.0 PLY files are read.")
+            if words[0] == "element":
+                elements.append((words[1], int(words[2]), []))
+            if words[0] == "property" and elements:
+                if len(elements) == 1 and (words[1] == "list" or words[1] not in _PLY_TYPES):
+                    raise Exception("Only scalar vertex properties are read.")
+                elements[-1][2].append((words[1], words[-1]))
+        if not elements or elements[0][0] != "vertex":
+            raise Exception("The first PLY element must be vertex.")
+        _, count, props = elements[0]
+        names = [n for _, n in props]
+        if any(c not in names for c in "xyz") or len(set(names)) != len(names):
+            raise Exception("The PLY vertices need x, y and z.")
+        dtype = np.dtype([(n, _PLY_TYPES[t]) for t, n in props])
+        blob = f.read(count * dtype.itemsize)
+        if len(blob) != count * dtype.itemsize:
+            raise Exception("Truncated PLY file.")
+        vertex = np.frombuffer(blob, dtype=dtype, count=count)
+    if not count:
+        return np.zeros((0, 3), np.float32)
+    return np.ascontiguousarray(np.stack([vertex[n] for n in "xyz"], axis=1), dtype=np.float32)
+
+
+def load_dtu_obs_mask(path, mask_name="ObsMask", bb_name="BB", res_name="Res"):
+    """``(mask (X, Y, Z) bool, bb_min (3,) float64, res float)`` from DTU's ``ObsMask/ObsMask<scan>_10.mat``: the variables
+    ``ObsMask``, ``BB`` (2 x 3, first row the minimum) and ``Res`` as DTU's evaluation program reads them.  Needs SciPy."""
+    from scipy.io import loadmat
+    mat = loadmat(path)
+    for name in (mask_name, bb_name, res_name):
+        if name not in mat:
+            raise KeyError("%s: no variable %r (has %s)" % (path, name, sorted(k for k in mat if not k.startswith("__"))))
+    mask = np.ascontiguousarray(np.asarray(mat[mask_name]) != 0)
+    bb = np.asarray(mat[bb_name], dtype=np.float64)
+    if mask.ndim != 3 or bb.shape != (2, 3):
+        raise ValueError("%s: %s must be a 3-D grid and %s 2 x 3" % (path, mask_name, bb_name))
+    return mask, bb[0].copy(), float(np.asarray(mat[res_name], dtype=np.float64).reshape(-1)[0])
+
+
+def load_dtu_plane(path, plane_name="P"):
+    """The four plane floats ``P`` of DTU's ``ObsMask/Plane<scan>.mat`` as a (4,) float64 array.  Needs SciPy."""
+    from scipy.io import loadmat
+    mat = loadmat(path)
+    if plane_name not in mat:
+        raise KeyError("%s: no variable %r" % (path, plane_name))
+    plane = np.asarray(mat[plane_name], dtype=np.float64).reshape(-1)
+    if plane.size != 4:
+        raise ValueError("%s: %s must have four values" % (path, plane_name))
+    return plane
