@@ -592,6 +592,41 @@ int pf_preprocess_resize_u8(const unsigned char* src, int V, int h_src, int w_sr
 int pf_preprocess_standardise_f32(const unsigned char* ref, const unsigned long long* sums, int V, int H, int W,
                                   float* out, void* stream);
 
+/* ---- the confidence filter of a whole scan, into the fusion (csrc/scan_filter.hip) -------------------------------
+ * What reference tools/depthfusion.py:153-170 does per view on files, for all V views in one launch and in the four
+ * interpolation modes of its -m/--inter_mode.  Specification: pointmvsnet_amd/scan.py (the resampling is this project's own
+ * statement of what cv2.resize does to float32; bit parity with OpenCV is neither claimed nor tested).
+ * pf_scan_filter_f32: filtered (V, h, w) = depth (V, h, w) where flow confidence >= flow_threshold and resized initial
+ *   confidence >= init_threshold, else 0; the comparisons are NumPy's depth[conf < thr] = 0, so a NaN confidence keeps
+ *   the depth.  kept (V) int32 receives the number of pixels per view that the filter did not zero (zeroed by the call,
+ *   integer atomics).  The flow confidence is EITHER flow_prob (V, 5, h, w), turned into a confidence by the rule of
+ *   pf_eval_flow_prob_f32, OR flow_conf (V, fh, fw); the other pointer is NULL.  init_conf is (V, ih, iw).  A confidence
+ *   map of the depth map's size is read as it is; any other size is resampled to (h, w) with the tap tables of its axes:
+ *   output row y reads the T source rows clamp(ys[y] + k, 0, s - 1), k = 0 .. T-1, with the weights yw[y * T + k]
+ *   (columns alike, xs / xw); T = 1 (PF_SCAN_NEAREST: the value itself, no product), 2 (BILINEAR), 4 (CUBIC),
+ *   8 (LANCZOS4).  The host composes the tables in float64 and passes the weights as float32; the kernel evaluates
+ *   horizontally first, then vertically, in float32, each sum in ascending tap order.  The tables of a map that needs
+ *   no resampling may be NULL.  flow_resized / init_resized: (V, h, w) or NULL, receive the confidences the comparisons
+ *   saw.
+ * pf_scan_filter_supported: 1 iff mode is one of the four, every size is >= 1, every map has at most 2^24 pixels,
+ *   h <= 65535 * PF_SCAN_FILTER_TILE_Y and the LDS tile of each resampled map fits 48 KiB:
+ *   4 * sy * (sx + PF_SCAN_FILTER_TILE_X) bytes with sy = (TILE_Y - 1) * s_h / h + T + 2 and
+ *   sx = (TILE_X - 1) * s_w / w + T + 2 (integer division) -- upsampling by any factor, shrinking by up to ~9 x with
+ *   LANCZOS4.  Anything else: PF_ERR_UNSUPPORTED.  V <= 65535. */
+#define PF_SCAN_NEAREST 0
+#define PF_SCAN_BILINEAR 1
+#define PF_SCAN_CUBIC 2
+#define PF_SCAN_LANCZOS4 4
+#define PF_SCAN_FILTER_TILE_X 32
+#define PF_SCAN_FILTER_TILE_Y 8
+int pf_scan_filter_supported(int mode, int h, int w, int fh, int fw, int ih, int iw);
+int pf_scan_filter_f32(const float* depth, const float* flow_prob, const float* flow_conf, int fh, int fw,
+                       const float* init_conf, int ih, int iw, int V, int h, int w, int mode, const int* flow_ys,
+                       const float* flow_yw, const int* flow_xs, const float* flow_xw, const int* init_ys,
+                       const float* init_yw, const int* init_xs, const float* init_xw, float flow_threshold,
+                       float init_threshold, float* filtered, int* kept, float* flow_resized, float* init_resized,
+                       void* stream);
+
 /* ==== Row Z : the training step (BASELINE config 4; reference train.py:72-82) ======================================
  * Hand-written backward for the convolution -> BatchNorm(batch statistics) -> ReLU blocks of ImageConv, VolumeConv
  * and the flow MLP (reference nn/conv.py:24-35,62-77,108-121,197-210; networks.py:84-167; model.py:40-43), replacing

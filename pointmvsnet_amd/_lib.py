@@ -119,6 +119,8 @@ PROTOTYPES = {
     "pf_cloud_above_plane_f32": ([_vp, _i64, _f, _f, _f, _f, _vp, _vp], _i),
     "pf_preprocess_resize_u8": ([_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp], _i),
     "pf_preprocess_standardise_f32": ([_vp, _vp, _i, _i, _i, _vp, _vp], _i),
+    "pf_scan_filter_supported": ([_i] * 7, _i),
+    "pf_scan_filter_f32": ([_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i] + [_vp] * 8 + [_f, _f, _vp, _vp, _vp, _vp, _vp], _i),
     "pf_softargmin_prob_f32": ([_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp], _i),
     "pf_bn_train_rows_f32": ([_vp, _i, _i, _i, _i, _d, _d, _vp, _vp, _vp, _vp, _f, _f, _i, _i, _vp, _i, _i, _i, _vp], _i),
     "pf_bn_bwd_reduce_f32": ([_vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _vp, _vp], _i),

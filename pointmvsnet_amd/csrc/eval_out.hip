@@ -21,28 +21,12 @@ __global__ __launch_bounds__(256) void eval_pack_map_kernel(const float* __restr
   dst[(flip ? h - 1 - y : y) * w + x] = src[i];
 }
 
-__device__ __forceinline__ float flow_confidence(const float* __restrict__ prob, int i, int hw) {
-  float p[5];
-#pragma unroll
-  for (int d = 0; d < 5; ++d) p[d] = prob[(int64_t)d * hw + i];
-  // np.sum(out_flow_prob_map * interval_list, axis=-1): float64 products, add.reduce = a0 + (((a1+a2)+a3)+a4)
-  const double a0 = (double)p[0] * -2.0, a1 = (double)p[1] * -1.0, a2 = (double)p[2] * 0.0;
-  const double a3 = (double)p[3] * 1.0, a4 = (double)p[4] * 2.0;
-  const double idx = (a0 + (((a1 + a2) + a3) + a4)) + 2.0;
-  int fl = (int)floor(idx);
-  int ce = fl + 1;
-  ce = ce < 0 ? 0 : (ce > 4 ? 4 : ce);                    // np.clip(pred_ceil, 0, 4)
-  fl = fl < 0 ? fl + 5 : fl;                              // NumPy fancy indexing wraps a negative index
-  fl = fl < 0 ? 0 : (fl > 4 ? 4 : fl);                    // (out of range would raise in NumPy; clamp, never fault)
-  return p[fl] + p[ce];
-}
-
 __global__ __launch_bounds__(256) void eval_flow_prob_kernel(const float* __restrict__ prob, float* __restrict__ dst,
                                                              int h, int w, int flip) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= h * w) return;
   const int y = i / w, x = i - y * w;
-  dst[(flip ? h - 1 - y : y) * w + x] = flow_confidence(prob, i, h * w);
+  dst[(flip ? h - 1 - y : y) * w + x] = pf_flow_confidence(prob, i, h * w);
 }
 
 __global__ __launch_bounds__(256) void eval_prob_filter_kernel(const float* __restrict__ depth,
@@ -104,11 +88,13 @@ int pf_eval_prob_filter_f32(const float* depth, const float* flow_conf, const fl
 }  // extern "C"
 
 // A build that is not hipcc's (no __HIP__: the host re-compilation of tests/hipemu, whose list of sources is fixed) gets
-// the next stage of the evaluation output, the fusion kernels, the scene input (preprocess.hip) and the point-cloud
-// evaluation (cloud_eval.hip) with this unit, so that such a library exports the whole C ABI.  hipcc compiles fusion.hip,
-// preprocess.hip and cloud_eval.hip as units of their own (build.SOURCES) and never takes this branch.
+// the next stage of the evaluation output, the fusion kernels, the scene input (preprocess.hip), the point-cloud
+// evaluation (cloud_eval.hip) and the scan's confidence filter (scan_filter.hip) with this unit, so that such a library
+// exports the whole C ABI.  hipcc compiles fusion.hip, preprocess.hip, cloud_eval.hip and scan_filter.hip as units of
+// their own (build.SOURCES) and never takes this branch.
 #if !defined(__HIP__)
 #include "fusion.hip"
 #include "preprocess.hip"
 #include "cloud_eval.hip"
+#include "scan_filter.hip"
 #endif

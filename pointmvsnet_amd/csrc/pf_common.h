@@ -180,3 +180,21 @@ __device__ __forceinline__ float pf_sample(const float* __restrict__ plane, cons
   const float d = plane[t.off[3]];
   return ((a * t.wgt[0] + b * t.wgt[1]) + c * t.wgt[2]) + d * t.wgt[3];
 }
+
+// ---- flow confidence of reference utils/eval_file_logger.py:48-62, shared by eval_out.hip and scan_filter.hip ----
+// prob (5, hw) hypothesis probabilities of one map -> p[floor(i)] + p[min(floor(i) + 1, 4)] at pixel i
+__device__ __forceinline__ float pf_flow_confidence(const float* __restrict__ prob, int i, int hw) {
+  float p[5];
+#pragma unroll
+  for (int d = 0; d < 5; ++d) p[d] = prob[(int64_t)d * hw + i];
+  // np.sum(out_flow_prob_map * interval_list, axis=-1): float64 products, add.reduce = a0 + (((a1+a2)+a3)+a4)
+  const double a0 = (double)p[0] * -2.0, a1 = (double)p[1] * -1.0, a2 = (double)p[2] * 0.0;
+  const double a3 = (double)p[3] * 1.0, a4 = (double)p[4] * 2.0;
+  const double idx = (a0 + (((a1 + a2) + a3) + a4)) + 2.0;
+  int fl = (int)floor(idx);
+  int ce = fl + 1;
+  ce = ce < 0 ? 0 : (ce > 4 ? 4 : ce);                    // np.clip(pred_ceil, 0, 4)
+  fl = fl < 0 ? fl + 5 : fl;                              // NumPy fancy indexing wraps a negative index
+  fl = fl < 0 ? 0 : (fl > 4 ? 4 : fl);                    // (out of range would raise in NumPy; clamp, never fault)
+  return p[fl] + p[ce];
+}

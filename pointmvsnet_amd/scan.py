@@ -1,0 +1,298 @@
+"""From the network's predictions to the point cloud of a scan, on the GPU: batched confidence filter into the fusion.
+
+The reference connects its stages through files: ``eval_file_logger`` writes every view's maps, ``tools/depthfusion.py``
+reads them back, filters each depth map by its two confidence maps (``probability_filter``, depthfusion.py:153-170) and
+hands the result to fusibile.  Here the predictions of all views stay on the device: ``ScanAccumulator`` collects them,
+``filter_depth_maps`` filters the V views in one launch (csrc/scan_filter.hip) and ``fuse_depth_maps`` takes its output.
+
+The filter
+----------
+``filtered = depth`` where ``flow_conf >= flow_prob_threshold`` and ``init_conf_resized >= init_prob_threshold``, else 0;
+the comparisons are NumPy's ``depth[conf < thr] = 0``, so a NaN confidence keeps the depth.  The flow confidence of raw
+``(V, 5, h, w)`` hypothesis probabilities is that of ``eval_file_logger`` (float64 index, float32 sum).  A confidence map
+of the depth map's size is used as it is; any other size is resized, as the reference does with ``cv2.resize`` in the mode
+of its ``-m/--inter_mode`` (default ``LANCZOS4``).
+
+The resampling specification
+----------------------------
+**This project's own statement of what cv2.resize does to float32 images.**  On uint8 OpenCV runs fixed-point kernels; on
+float32 it is plain separable float arithmetic with closed-form weights, which is stated here.  OpenCV is not a
+dependency: bit parity with ``cv2.resize`` is neither claimed nor tested.  For destination size ``n`` from source size
+``s``, per axis and destination index ``i``:
+
+* ``NEAREST``: one tap at ``min(floor(i * (s / n)), s - 1)`` with weight 1 (the rule of
+  ``eval_file_logger._resize_nearest``; the value itself, no product).
+* the others: ``f = (i + 0.5) * (s / n) - 0.5``, ``i0 = floor(f)``, ``t = f - i0``; taps at ``i0 + k``, each **clamped to
+  [0, s - 1]** (replicate border); no prefiltering when shrinking.
+
+  - ``BILINEAR``: ``k = 0, 1``, weights ``(1 - t, t)``.
+  - ``CUBIC``: ``k = -1 .. 2``, Keys' kernel with ``A = -0.75``:
+    ``w(-1) = ((A (t + 1) - 5 A) (t + 1) + 8 A) (t + 1) - 4 A``, ``w(0) = ((A + 2) t - (A + 3)) t^2 + 1``,
+    ``w(1) = ((A + 2) (1 - t) - (A + 3)) (1 - t)^2 + 1``, ``w(2) = 1 - w(-1) - w(0) - w(1)``.
+  - ``LANCZOS4``: ``k = -3 .. 4``, ``L(t - k)`` with ``L(x) = sinc(x) sinc(x / 4)`` for ``|x| < 4`` (``sinc(x) =
+    sin(pi x) / (pi x)``), divided by their sum; at ``t = 0`` exactly ``(0, 0, 0, 1, 0, 0, 0, 0)``.
+
+``resize_taps`` composes the tables (first tap's index, weights) in float64; the kernel gets the weights as float32 and
+evaluates horizontally first, then vertically, in float32, each sum in ascending tap order.  Departures from OpenCV that
+are known: OpenCV computes its LANCZOS4 weights with a rotation recurrence in float32 and its CUBIC weights in float32,
+so its results differ from this statement in the last bits; a zero weight times an infinite sample is NaN here as there.
+"""
+import numpy as np
+import torch
+
+from . import _lib
+from .fusion import fuse_depth_maps
+from .utils.eval_file_logger import _resize_nearest, _scene_paths
+from .utils.io import write_ply
+
+# name -> (PF_SCAN_* of include/pointflow_hip.h, taps per axis)
+MODES = {"NEAREST": (0, 1), "BILINEAR": (1, 2), "CUBIC": (2, 4), "LANCZOS4": (4, 8)}
+
+
+def _mode(mode):
+    if mode not in MODES:
+        raise ValueError("unknown interpolation mode %r (one of %s)" % (mode, ", ".join(sorted(MODES))))
+    return MODES[mode]
+
+
+def resize_taps(src, dst, mode):
+    """The tap tables of one axis, ``(start (dst,) int64, weights (dst, T) float64)``: destination index ``i`` reads the
+    source indices ``clip(start[i] + k, 0, src - 1)``, ``k = 0 .. T-1``, with ``weights[i, k]`` (module docstring)."""
+    _, T = _mode(mode)
+    src, dst = int(src), int(dst)
+    if src < 1 or dst < 1:
+        raise ValueError("resize_taps: sizes must be at least 1")
+    i = np.arange(dst, dtype=np.float64)
+    scale = src / float(dst)
+    if mode == "NEAREST":
+        return np.minimum(np.floor(i * scale).astype(np.int64), src - 1), np.ones((dst, 1))
+    f = (i + 0.5) * scale - 0.5
+    i0 = np.floor(f)
+    t = f - i0
+    if mode == "BILINEAR":
+        weights = np.stack([1.0 - t, t], axis=1)
+    elif mode == "CUBIC":
+        A = -0.75
+        w0 = ((A * (t + 1.0) - 5.0 * A) * (t + 1.0) + 8.0 * A) * (t + 1.0) - 4.0 * A
+        w1 = ((A + 2.0) * t - (A + 3.0)) * t * t + 1.0
+        w2 = ((A + 2.0) * (1.0 - t) - (A + 3.0)) * (1.0 - t) * (1.0 - t) + 1.0
+        weights = np.stack([w0, w1, w2, 1.0 - w0 - w1 - w2], axis=1)
+    else:
+        x = t[:, None] - np.arange(-3.0, 5.0)[None, :]
+        weights = np.where(np.abs(x) < 4.0, np.sinc(x) * np.sinc(x / 4.0), 0.0)
+        weights = weights / weights.sum(axis=1, keepdims=True)
+        weights[t == 0.0] = np.eye(8)[3]
+    return i0.astype(np.int64) - (T // 2 - 1), weights
+
+
+def _tables(src_hw, dst_hw, mode, dev):
+    """The four device tables of one map (ys, yw, xs, xw), or Nones when the map needs no resampling."""
+    if tuple(src_hw) == tuple(dst_hw):
+        return None, None, None, None
+    out = []
+    for s, n in zip(src_hw, dst_hw):
+        start, weights = resize_taps(s, n, mode)
+        out.append(torch.from_numpy(start.astype(np.int32)).to(dev))
+        out.append(torch.from_numpy(np.ascontiguousarray(weights, dtype=np.float32)).to(dev))
+    return tuple(out)
+
+
+def filter_depth_maps(depths, flow_probs, init_probs, init_prob_threshold=0.2, flow_prob_threshold=0.1, mode="LANCZOS4",
+                      return_kept=False, return_stages=False):
+    """The confidence filter of the module docstring for all views at once, on the GPU.
+
+    ``depths`` (V, h, w); ``flow_probs`` (V, 5, h, w) raw hypothesis probabilities or (V, fh, fw) confidences;
+    ``init_probs`` (V, ih, iw) (a (V, 1, ih, iw) tensor is accepted).  Returns ``filtered`` (V, h, w) float32 contiguous,
+    what ``fuse_depth_maps`` takes; with ``return_kept`` also the (V,) int32 count of pixels per view that the filter did
+    not zero; with ``return_stages`` last the dict of the confidences the comparisons saw, ``flow_conf`` and ``init_conf``
+    (V, h, w).  There is no CPU path."""
+    code, T = _mode(mode)
+    for name, t in (("depths", depths), ("flow_probs", flow_probs), ("init_probs", init_probs)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("filter_depth_maps: %s must be a tensor" % name)
+    if depths.dim() != 3:
+        raise ValueError("filter_depth_maps: depths must be (V, h, w)")
+    V, h, w = (int(s) for s in depths.shape)
+    if init_probs.dim() == 4 and init_probs.shape[1] == 1:
+        init_probs = init_probs[:, 0]
+    if init_probs.dim() != 3 or init_probs.shape[0] != V:
+        raise ValueError("filter_depth_maps: init_probs must be (V, ih, iw) with the V of depths")
+    raw = flow_probs.dim() == 4
+    if raw and tuple(flow_probs.shape) != (V, 5, h, w):
+        raise ValueError("filter_depth_maps: raw flow_probs must be (V, 5, h, w) of the depth maps' size")
+    if not raw and (flow_probs.dim() != 3 or flow_probs.shape[0] != V):
+        raise ValueError("filter_depth_maps: flow_probs must be (V, 5, h, w) or (V, fh, fw) with the V of depths")
+    if min(init_probs.shape[1:]) < 1 or min(flow_probs.shape[-2:]) < 1:
+        raise ValueError("filter_depth_maps: empty confidence maps")
+    _lib.require_gpu(depths, flow_probs, init_probs)
+    dev = depths.device
+    depths = depths.contiguous().float()
+    flow_probs = flow_probs.contiguous().float()
+    init_probs = init_probs.contiguous().float()
+    fh, fw = (h, w) if raw else (int(s) for s in flow_probs.shape[1:])
+    ih, iw = (int(s) for s in init_probs.shape[1:])
+    with _lib.on_device(dev):
+        filtered = torch.empty((V, h, w), dtype=torch.float32, device=dev)
+        kept = torch.zeros((V,), dtype=torch.int32, device=dev)
+        stages = None
+        if return_stages:
+            stages = {"flow_conf": torch.empty((V, h, w), dtype=torch.float32, device=dev),
+                      "init_conf": torch.empty((V, h, w), dtype=torch.float32, device=dev)}
+        if V and h and w:
+            if not _lib.load().pf_scan_filter_supported(code, h, w, fh, fw, ih, iw):
+                raise ValueError("filter_depth_maps: sizes %s <- flow %s, init %s are outside what the kernel is built for "
+                                 "(pf_scan_filter_supported, include/pointflow_hip.h)" % ((h, w), (fh, fw), (ih, iw)))
+            flow_t = _tables((fh, fw), (h, w), mode, dev)
+            init_t = _tables((ih, iw), (h, w), mode, dev)
+            # per pixel: depth, the flow confidence's input, the coarse confidence's share, the output
+            algo = V * (h * w * (4 + (20 if raw else 0) + 4) + (0 if raw else 4 * fh * fw) + 4 * ih * iw)
+            _lib.call("pf_scan_filter_f32", _lib.ptr(depths), _lib.ptr(flow_probs if raw else None),
+                      _lib.ptr(None if raw else flow_probs), fh, fw, _lib.ptr(init_probs), ih, iw, V, h, w, code,
+                      *([_lib.ptr(t) for t in flow_t] + [_lib.ptr(t) for t in init_t]), float(flow_prob_threshold),
+                      float(init_prob_threshold), _lib.ptr(filtered), _lib.ptr(kept),
+                      _lib.ptr(stages["flow_conf"] if stages else None), _lib.ptr(stages["init_conf"] if stages else None),
+                      _lib.stream(), algo_bytes=algo, tag=mode)
+    out = (filtered,) + ((kept,) if return_kept else ()) + ((stages,) if return_stages else ())
+    return out[0] if len(out) == 1 else out
+
+
+class ScanAccumulator(object):
+    """Collects the predictions of the ``view_num`` views of one scan on the device and turns them into the point cloud.
+
+    ``add(data_batch, preds)`` after every forward; then ``filtered()``, ``cameras()``, ``fuse()``, ``write_ply(path)``.
+    ``name`` is the depth map that is fused (``preds[name]``, ``preds[name + "_prob"]``), ``mode`` and the thresholds are
+    those of ``filter_depth_maps``; ``keep_images`` keeps the views' images for the cloud's colours."""
+
+    def __init__(self, view_num, name="flow2", mode="LANCZOS4", init_prob_threshold=0.2, flow_prob_threshold=0.1,
+                 keep_images=True):
+        _mode(mode)
+        if int(view_num) < 1:
+            raise ValueError("ScanAccumulator: view_num must be at least 1")
+        self.view_num, self.name, self.mode = int(view_num), name, mode
+        self.init_prob_threshold, self.flow_prob_threshold = float(init_prob_threshold), float(flow_prob_threshold)
+        self.keep_images = keep_images
+        self._seen = [False] * self.view_num
+        self._depth = self._flow = self._init = self._images = None
+        self._with_image = 0
+        self._K = np.zeros((self.view_num, 3, 3))
+        self._E = np.zeros((self.view_num, 4, 4))
+
+    def add(self, data_batch, preds, view_index=None):
+        """Store one view.  ``view_index`` defaults to the index ``eval_file_logger`` derives from
+        ``data_batch["ref_img_path"]`` (``rect_007_...`` -> 6)."""
+        if view_index is None:
+            path = data_batch["ref_img_path"]
+            view_index = _scene_paths(path if isinstance(path, str) else path[0], "")[1]
+        v = int(view_index)
+        if not 0 <= v < self.view_num:
+            raise ValueError("ScanAccumulator: view %d of %d" % (v, self.view_num))
+        if self._seen[v]:
+            raise ValueError("ScanAccumulator: view %d was added before" % v)
+        for key in (self.name, self.name + "_prob", "coarse_prob_map"):
+            if key not in preds:
+                raise ValueError("ScanAccumulator: the predictions have no %r" % key)
+        depth, flow, init = preds[self.name][0, 0], preds[self.name + "_prob"][0], preds["coarse_prob_map"][0, 0]
+        _lib.require_gpu(depth, flow, init)
+        if self._depth is None:
+            dev, V = depth.device, self.view_num
+            self._depth = torch.zeros((V,) + tuple(depth.shape), dtype=torch.float32, device=dev)
+            self._flow = torch.zeros((V,) + tuple(flow.shape), dtype=torch.float32, device=dev)
+            self._init = torch.zeros((V,) + tuple(init.shape), dtype=torch.float32, device=dev)
+        for buf, t, what in ((self._depth, depth, "depth map"), (self._flow, flow, "flow probabilities"),
+                             (self._init, init, "coarse confidence")):
+            if tuple(t.shape) != tuple(buf.shape[1:]):
+                raise ValueError("ScanAccumulator: view %d's %s is %s, the first view's %s"
+                                 % (v, what, tuple(t.shape), tuple(buf.shape[1:])))
+        # Enqueued on the current stream, no host synchronisation: GraphedForward / LanedForward hand out STATIC buffers that
+        # the next replay on this stream overwrites, and the replay is ordered behind these copies (the hazard that the
+        # comment in AsyncEvalWriter.submit describes; there the packs run on a side stream, here on the producer's own).
+        self._depth[v].copy_(depth, non_blocking=True)
+        self._flow[v].copy_(flow, non_blocking=True)
+        self._init[v].copy_(init, non_blocking=True)
+        h, w = (int(s) for s in depth.shape)
+        cams = data_batch.get("cam_params_list_host")
+        if cams is None:
+            cams = data_batch["cam_params_list"].detach().cpu()
+        cam = cams.numpy()[0, 0].copy()
+        ref = data_batch.get("ref_img")
+        ref_h = int(ref.shape[1]) if ref is not None else int(data_batch["img_list"].shape[3])
+        cam[1, :2, :3] *= (float(h) / float(ref_h))            # cam_file of eval_file_logger_host, in the cameras' dtype
+        self._K[v], self._E[v] = cam[1, :3, :3], cam[0]
+        if self.keep_images and ref is not None:
+            img = torch.as_tensor(ref)[0]
+            if img.dim() != 3 or img.shape[2] != 3 or img.dtype != torch.uint8:
+                raise ValueError("ScanAccumulator: ref_img must be (1, H, W, 3) uint8")
+            if tuple(img.shape[:2]) != (h, w):                 # _load_image: nearest-resized, then BGR -> RGB
+                ys = np.arange(img.shape[0])[:, None]
+                xs = np.arange(img.shape[1])[None, :]
+                ys, xs = _resize_nearest(ys, h, 1)[:, 0], _resize_nearest(xs, 1, w)[0]
+                img = img[torch.from_numpy(ys).to(img.device)][:, torch.from_numpy(xs).to(img.device)]
+            if self._images is None:
+                self._images = torch.zeros((self.view_num, h, w, 3), dtype=torch.uint8, device=self._depth.device)
+            self._images[v].copy_(img.flip(-1), non_blocking=True)
+            self._with_image += 1
+        self._seen[v] = True
+
+    def _require_complete(self, what):
+        missing = [v for v, s in enumerate(self._seen) if not s]
+        if missing:
+            raise ValueError("ScanAccumulator.%s: views %s have not been added" % (what, missing))
+
+    def predictions(self):
+        """The stacked ``(depths (V, h, w), flow_probs (V, 5, h, w), init_probs (V, ih, iw))`` of the added views."""
+        self._require_complete("predictions")
+        return self._depth, self._flow, self._init
+
+    def filtered(self, return_kept=False):
+        """``filter_depth_maps`` of the accumulated views: (V, h, w)."""
+        self._require_complete("filtered")
+        return filter_depth_maps(self._depth, self._flow, self._init, self.init_prob_threshold, self.flow_prob_threshold,
+                                 self.mode, return_kept=return_kept)
+
+    def cameras(self):
+        """``(intrinsics (V, 3, 3) of the depth maps' grid, extrinsics (V, 4, 4))`` as float64 NumPy."""
+        self._require_complete("cameras")
+        return self._K.copy(), self._E.copy()
+
+    def images(self):
+        """(V, h, w, 3) uint8 RGB on the device, or None unless every view came with a ``ref_img``."""
+        return self._images if self._with_image == self.view_num else None
+
+    def fuse(self, disp_threshold=0.12, num_consistent=3, depth_min=1e-3, depth_max=1e5):
+        """``(points (N, 3) float32, colours (N, 3) uint8 or None)`` through ``fuse_depth_maps``."""
+        self._require_complete("fuse")
+        K, E = self.cameras()
+        return fuse_depth_maps(self.filtered(), K, E, images=self.images(), disp_threshold=disp_threshold,
+                               num_consistent=num_consistent, depth_min=depth_min, depth_max=depth_max)
+
+    def write_ply(self, path, **fuse_kwargs):
+        """Fuse and write the cloud to ``path``; returns ``(points, colours)``."""
+        points, colours = self.fuse(**fuse_kwargs)
+        write_ply(path, points.cpu().numpy(), None if colours is None else colours.cpu().numpy())
+        return points, colours
+
+
+def reconstruct_scan(model, batches, img_scales=(0.125, 0.25, 0.5), inter_scales=(1.0, 0.75, 0.15), view_num=None,
+                     fuse_kwargs=None, **accumulator_kwargs):
+    """Run ``model`` on every ``data_batch`` of one scan (any iterable; one view as the reference each), accumulate the
+    views and fuse them: ``(points, colours, accumulator)``.
+
+    A ``torch.nn.Module`` is called as the evaluation forward, ``model(data_batch, img_scales, inter_scales, isFlow=True,
+    isTest=True)`` under ``torch.no_grad()``; anything else (a ``GraphedForward``) as ``model(data_batch)``.  ``view_num``
+    defaults to ``len(batches)``; a batch may carry its ``view_index``, else ``ref_img_path`` tells it, else its position."""
+    if view_num is None:
+        batches = list(batches)
+        view_num = len(batches)
+    acc = ScanAccumulator(view_num, **accumulator_kwargs)
+    with torch.no_grad():
+        for position, data_batch in enumerate(batches):
+            if isinstance(model, torch.nn.Module):
+                preds = model(data_batch, img_scales, inter_scales, isFlow=True, isTest=True)
+            else:
+                preds = model(data_batch)
+            index = data_batch.get("view_index")
+            if index is None and "ref_img_path" not in data_batch:
+                index = position
+            acc.add(data_batch, preds, view_index=index)
+    points, colours = acc.fuse(**(fuse_kwargs or {}))
+    return points, colours, acc

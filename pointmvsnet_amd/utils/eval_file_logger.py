@@ -256,7 +256,9 @@ def _resize_nearest(img, h, w):
 def probability_filter(scene_folder, init_prob_threshold, flow_prob_threshold, name, view_num, mode="NEAREST"):
     """The fusion pre-step of reference tools/depthfusion.py:153-170 on the files eval_file_logger wrote: depth := 0
     where the flow or the (resized) initial confidence is below its threshold -> ``%08d_<name>_prob_filtered.pfm``.
-    Only nearest resizing is built (the other cv2 interpolation modes are OpenCV's own fixed-point kernels)."""
+    This file-based function resizes by the nearest rule only.  (OpenCV's fixed-point kernels are what it runs on uint8;
+    on float32 maps the other modes are plain separable float arithmetic: ``pointmvsnet_amd.scan.filter_depth_maps``
+    states and runs BILINEAR, CUBIC and LANCZOS4 on the GPU.)"""
     if mode not in ("NEAREST", 0):
         raise NotImplementedError("probability_filter: only cv2.INTER_NEAREST resizing is implemented")
     for v in range(view_num):

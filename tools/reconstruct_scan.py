@@ -1,0 +1,104 @@
+"""Reconstruct one DTU scan on the GPU, from the image folder to the point cloud (pointmvsnet_amd/scan.py): input and
+preprocessing, the network, the batched confidence filter, the fusion and, optionally, the score -- no intermediate files.
+
+    python tools/reconstruct_scan.py --root DTU --scan 9 --weights model.pth --out scan9.ply \
+        [--mode LANCZOS4] [--init-prob-threshold 0.2] [--flow-prob-threshold 0.1] [--name flow2] \
+        [--gt stl009_total.ply --obs-mask ObsMask9_10.mat --plane Plane9.mat]
+
+``--weights`` is a ``torch.load``-able file: its ``"model"`` entry if it has one, a leading ``module.`` stripped from the
+keys.  Prints one JSON line: the number of points, the kept share per view and, with ``--gt``, the dict of
+``evaluate_point_cloud``.
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def load_weights(model, path):
+    import torch
+    state = torch.load(path, map_location="cpu")
+    if isinstance(state, dict) and "model" in state:
+        state = state["model"]
+    model.load_state_dict({(k[len("module."):] if k.startswith("module.") else k): v for k, v in state.items()})
+
+
+def batches_of(dataset, dev):
+    """The dataset's items as the model's batches of one: a leading batch axis, device tensors, host copies of the cameras."""
+    import torch
+    for index in range(len(dataset)):
+        item = dataset[index]
+        batch = {"ref_img_path": item["ref_img_path"]}
+        for key in ("img_list", "cam_params_list", "mean", "std", "ref_img"):
+            batch[key] = torch.as_tensor(item[key])[None]
+        batch["cam_params_list_host"] = batch["cam_params_list"]
+        batch["mean_host"], batch["std_host"] = batch["mean"], batch["std"]
+        for key in ("img_list", "cam_params_list", "mean", "std"):
+            batch[key] = batch[key].to(dev)
+        yield batch
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--root", required=True, help="the DTU folder (Cameras/, Eval/Rectified/scan<N>/)")
+    ap.add_argument("--scan", type=int, required=True)
+    ap.add_argument("--out", required=True, help="the point cloud to write (binary PLY)")
+    ap.add_argument("--weights", default=None, help="a torch.load-able state dict (default: seeded synthetic weights)")
+    ap.add_argument("--mode", default="LANCZOS4", choices=["NEAREST", "BILINEAR", "CUBIC", "LANCZOS4"])
+    ap.add_argument("--init-prob-threshold", type=float, default=0.2)
+    ap.add_argument("--flow-prob-threshold", type=float, default=0.1)
+    ap.add_argument("--disp-threshold", type=float, default=0.12)
+    ap.add_argument("--num-consistent", type=int, default=3)
+    ap.add_argument("--name", default="flow2")
+    ap.add_argument("--num-view", type=int, default=5)
+    ap.add_argument("--height", type=int, default=960)
+    ap.add_argument("--width", type=int, default=1280)
+    ap.add_argument("--num-virtual-plane", type=int, default=96)
+    ap.add_argument("--interval-scale", type=float, default=2.13)
+    ap.add_argument("--img-scales", type=float, nargs="+", default=[0.125, 0.25, 0.5])
+    ap.add_argument("--inter-scales", type=float, nargs="+", default=[1.0, 0.75, 0.15])
+    ap.add_argument("--lighting", type=int, default=3)
+    ap.add_argument("--gt", default=None, help="the scan's ground-truth cloud (PLY): score the result")
+    ap.add_argument("--obs-mask", default=None, help="DTU's ObsMask<scan>_10.mat")
+    ap.add_argument("--plane", default=None, help="DTU's Plane<scan>.mat")
+    ap.add_argument("--device", default="cuda:0")
+    args = ap.parse_args()
+    import torch
+    from pointmvsnet_amd import evaluation, scan, synthetic
+    from pointmvsnet_amd.dataset import DTUDataset
+    from pointmvsnet_amd.model import PointMVSNet
+    from pointmvsnet_amd.utils import io
+    dev = torch.device(args.device)
+    net = PointMVSNet()
+    if args.weights:
+        load_weights(net, args.weights)
+    else:
+        synthetic.seed_weights(net, seed=0)
+    net = net.to(dev).train()                                # the reference evaluates in train() mode (test.py:58)
+    dataset = DTUDataset(args.root, "test", num_view=args.num_view, height=args.height, width=args.width,
+                         num_virtual_plane=args.num_virtual_plane, interval_scale=args.interval_scale, device=dev,
+                         scans=[args.scan], lightings=[args.lighting])
+    points, colours, acc = scan.reconstruct_scan(
+        net, batches_of(dataset, dev), tuple(args.img_scales), tuple(args.inter_scales), view_num=len(dataset),
+        fuse_kwargs={"disp_threshold": args.disp_threshold, "num_consistent": args.num_consistent}, name=args.name,
+        mode=args.mode, init_prob_threshold=args.init_prob_threshold, flow_prob_threshold=args.flow_prob_threshold)
+    io.write_ply(args.out, points.cpu().numpy(), None if colours is None else colours.cpu().numpy())
+    filtered, kept = acc.filtered(return_kept=True)
+    out = {"scan": args.scan, "views": len(dataset), "mode": args.mode, "points": int(points.shape[0]), "out": args.out,
+           "kept_share_per_view": [k / float(filtered[0].numel()) for k in kept.cpu().tolist()]}
+    if args.gt:
+        kw = {}
+        if args.obs_mask:
+            mask, bb_min, res = io.load_dtu_obs_mask(args.obs_mask)
+            kw.update(obs_mask=torch.from_numpy(mask), bb_min=bb_min, res=res)
+        if args.plane:
+            kw.update(plane=io.load_dtu_plane(args.plane))
+        out["score"] = evaluation.evaluate_point_cloud(points, torch.from_numpy(io.load_ply_points(args.gt)).to(dev), **kw)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
