@@ -530,6 +530,30 @@ int pf_fuse_mark(const int* count, const int* match, unsigned char* used, unsign
 int pf_fuse_compact_f32(const unsigned char* emit, const int64_t* rank, const float* point, const unsigned char* colour,
                         int64_t n, int64_t rows, float* out_point, unsigned char* out_colour, void* stream);
 
+/* ---- round-trip geometric consistency filter (csrc/geo_filter.hip) ----------------------------------------------
+ * The check of the PyTorch MVS code bases that followed the reference (MVSNet-pytorch, CasMVSNet): the reference has no
+ * such step and OpenCV is not a dependency, so the specification is this project's own (pointmvsnet_amd/geometric.py,
+ * DESIGN.md section 9).  Maps and pixel centres as above.  Only the listed pairs are composed:
+ *   view_maps (V, PF_FUSE_VIEW_FLOATS) as above
+ *   sources   (V, M) int32: the source views of view i in the order they are visited; -1 (a pad) and i itself are skipped
+ *   pair_maps (V, M, 2, PF_FUSE_PAIR_FLOATS): entry [i][m][0] is the i -> j layout above for j = sources[i][m],
+ *             entry [i][m][1] the same for j -> i (fb is not read)
+ * pf_geo_filter_f32: per pixel p = (x, y) of view i with depth_min < d < depth_max, d = d_i(p), and listed source j:
+ *   1. q = (M_ij (x+.5, y+.5, 1)) d + T_ij, (u, v) = q.xy / q.z; skip j if q.z <= 0
+ *   2. (fx, fy) = (u - .5, v - .5), (x0, y0) = floor(fx, fy); skip j unless 0 <= x0, x0 + 1 <= w - 1, 0 <= y0,
+ *      y0 + 1 <= h - 1 (no border replication) and the four taps d_j(y0.., x0..) are inside (depth_min, depth_max);
+ *      ds = top (1 - wy) + bot wy, top = t00 (1 - wx) + t01 wx, bot = t10 (1 - wx) + t11 wx, wx = fx - x0, wy = fy - y0
+ *   3. q' = (M_ji (u, v, 1)) ds + T_ji, d' = q'.z, (u', v') = q'.xy / d'
+ *   4. j is consistent iff d' > 0, sqrt((u' - (x+.5))^2 + (v' - (y+.5))^2) < pix_threshold and
+ *      |d' - d| / d < rel_depth_threshold
+ *   count (V,h,w) = consistent sources; emit (V,h,w) = (count >= num_consistent); depth_avg (V,h,w) =
+ *   (d + sum of the consistent d', in list order) / (count + 1) where emit, else 0; point (V,h,w,3) = the
+ *   back-projection of p at depth_avg where emit, else 0.  Pixels without depth: count 0, emit 0.
+ *   A pixel's colour is its own, so the colours do not pass through this call: pf_fuse_compact_f32 takes the images. */
+int pf_geo_filter_f32(const float* depth, const float* view_maps, const int* sources, const float* pair_maps, int V, int M,
+                      int h, int w, float pix_threshold, float rel_depth_threshold, int num_consistent, float depth_min,
+                      float depth_max, int* count, float* depth_avg, float* point, unsigned char* emit, void* stream);
+
 /* ---- point-cloud evaluation: thinning and nearest distances between unordered clouds (csrc/cloud_eval.hip) -------
  * DTU's accuracy / completeness step, which the reference does not have (a separate MATLAB program).  The specification
  * is this project's own (pointmvsnet_amd/evaluation.py).  A cloud is searched through a sparse grid

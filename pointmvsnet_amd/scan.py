@@ -42,6 +42,7 @@ import torch
 
 from . import _lib
 from .fusion import fuse_depth_maps
+from .geometric import geometric_filter
 from .utils.eval_file_logger import _resize_nearest, _scene_paths
 from .utils.io import write_ply
 
@@ -258,15 +259,32 @@ class ScanAccumulator(object):
         """(V, h, w, 3) uint8 RGB on the device, or None unless every view came with a ``ref_img``."""
         return self._images if self._with_image == self.view_num else None
 
-    def fuse(self, disp_threshold=0.12, num_consistent=3, depth_min=1e-3, depth_max=1e5):
-        """``(points (N, 3) float32, colours (N, 3) uint8 or None)`` through ``fuse_depth_maps``."""
+    def geometric(self, sources=None, **kwargs):
+        """``geometric.geometric_filter`` of ``filtered()``, ``cameras()`` and ``images()``: ``(depth_avg, mask, count)`` and,
+        unless ``return_points=False``, ``points`` and ``colours``.  ``sources``: the (V, M) table of source views (None: all
+        other views); ``kwargs``: its thresholds."""
+        self._require_complete("geometric")
+        K, E = self.cameras()
+        return geometric_filter(self.filtered(), K, E, images=self.images(), sources=sources, **kwargs)
+
+    def fuse(self, disp_threshold=0.12, num_consistent=3, depth_min=1e-3, depth_max=1e5, method="disparity", **kwargs):
+        """``(points (N, 3) float32, colours (N, 3) uint8 or None)``: with ``method="disparity"`` through
+        ``fuse_depth_maps``; with ``method="roundtrip"`` the cloud of ``geometric()`` (``disp_threshold`` is not used;
+        ``kwargs``: ``sources``, ``pix_threshold``, ``rel_depth_threshold``)."""
+        if method not in ("disparity", "roundtrip"):
+            raise ValueError("ScanAccumulator.fuse: unknown method %r (disparity or roundtrip)" % (method,))
         self._require_complete("fuse")
+        if method == "roundtrip":
+            return self.geometric(num_consistent=num_consistent, depth_min=depth_min, depth_max=depth_max, **kwargs)[3:5]
+        if kwargs:
+            raise TypeError("ScanAccumulator.fuse: %s belong to method=\"roundtrip\"" % ", ".join(sorted(kwargs)))
         K, E = self.cameras()
         return fuse_depth_maps(self.filtered(), K, E, images=self.images(), disp_threshold=disp_threshold,
                                num_consistent=num_consistent, depth_min=depth_min, depth_max=depth_max)
 
     def write_ply(self, path, **fuse_kwargs):
-        """Fuse and write the cloud to ``path``; returns ``(points, colours)``."""
+        """Fuse (``fuse_kwargs``: those of ``fuse``, ``method`` among them) and write the cloud to ``path``; returns
+        ``(points, colours)``."""
         points, colours = self.fuse(**fuse_kwargs)
         write_ply(path, points.cpu().numpy(), None if colours is None else colours.cpu().numpy())
         return points, colours

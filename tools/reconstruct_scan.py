@@ -3,10 +3,14 @@ preprocessing, the network, the batched confidence filter, the fusion and, optio
 
     python tools/reconstruct_scan.py --root DTU --scan 9 --weights model.pth --out scan9.ply \
         [--mode LANCZOS4] [--init-prob-threshold 0.2] [--flow-prob-threshold 0.1] [--name flow2] \
+        [--fusion roundtrip --num-src 10 --save-depth DIR] \
         [--gt stl009_total.ply --obs-mask ObsMask9_10.mat --plane Plane9.mat]
 
 ``--weights`` is a ``torch.load``-able file: its ``"model"`` entry if it has one, a leading ``module.`` stripped from the
-keys.  Prints one JSON line: the number of points, the kept share per view and, with ``--gt``, the dict of
+keys.  ``--fusion roundtrip`` replaces the disparity fusion by the round-trip consistency filter
+(pointmvsnet_amd/geometric.py) against the first ``--num-src`` views that ``Cameras/pair.txt`` lists for every view (0: all
+other views); ``--save-depth DIR`` writes that filter's averaged depth map and mask of every view as ``%08d_geo.pfm`` and
+``%08d_geo_mask.pfm``.  Prints one JSON line: the number of points, the kept share per view and, with ``--gt``, the dict of
 ``evaluate_point_cloud``.
 """
 import argparse
@@ -52,6 +56,11 @@ def main():
     ap.add_argument("--flow-prob-threshold", type=float, default=0.1)
     ap.add_argument("--disp-threshold", type=float, default=0.12)
     ap.add_argument("--num-consistent", type=int, default=3)
+    ap.add_argument("--fusion", default="disparity", choices=["disparity", "roundtrip"])
+    ap.add_argument("--num-src", type=int, default=10, help="roundtrip: source views per view from pair.txt (0: all others)")
+    ap.add_argument("--pix-threshold", type=float, default=1.0)
+    ap.add_argument("--rel-depth-threshold", type=float, default=0.01)
+    ap.add_argument("--save-depth", default=None, help="folder for the round-trip filter's %%08d_geo.pfm / %%08d_geo_mask.pfm")
     ap.add_argument("--name", default="flow2")
     ap.add_argument("--num-view", type=int, default=5)
     ap.add_argument("--height", type=int, default=960)
@@ -67,7 +76,7 @@ def main():
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args()
     import torch
-    from pointmvsnet_amd import evaluation, scan, synthetic
+    from pointmvsnet_amd import evaluation, geometric, scan, synthetic
     from pointmvsnet_amd.dataset import DTUDataset
     from pointmvsnet_amd.model import PointMVSNet
     from pointmvsnet_amd.utils import io
@@ -81,14 +90,29 @@ def main():
     dataset = DTUDataset(args.root, "test", num_view=args.num_view, height=args.height, width=args.width,
                          num_virtual_plane=args.num_virtual_plane, interval_scale=args.interval_scale, device=dev,
                          scans=[args.scan], lightings=[args.lighting])
+    sources = geometric.sources_from_pairs(dataset.cluster_list, len(dataset), args.num_src) if args.num_src > 0 else None
+    geo_kwargs = {"sources": sources, "pix_threshold": args.pix_threshold, "rel_depth_threshold": args.rel_depth_threshold,
+                  "num_consistent": args.num_consistent}
+    fuse_kwargs = {"disp_threshold": args.disp_threshold, "num_consistent": args.num_consistent}
+    if args.fusion == "roundtrip":
+        fuse_kwargs = dict(geo_kwargs, method="roundtrip")
     points, colours, acc = scan.reconstruct_scan(
         net, batches_of(dataset, dev), tuple(args.img_scales), tuple(args.inter_scales), view_num=len(dataset),
-        fuse_kwargs={"disp_threshold": args.disp_threshold, "num_consistent": args.num_consistent}, name=args.name,
+        fuse_kwargs=fuse_kwargs, name=args.name,
         mode=args.mode, init_prob_threshold=args.init_prob_threshold, flow_prob_threshold=args.flow_prob_threshold)
     io.write_ply(args.out, points.cpu().numpy(), None if colours is None else colours.cpu().numpy())
     filtered, kept = acc.filtered(return_kept=True)
-    out = {"scan": args.scan, "views": len(dataset), "mode": args.mode, "points": int(points.shape[0]), "out": args.out,
+    out = {"scan": args.scan, "views": len(dataset), "mode": args.mode, "fusion": args.fusion, "points": int(points.shape[0]), "out": args.out,
            "kept_share_per_view": [k / float(filtered[0].numel()) for k in kept.cpu().tolist()]}
+    if args.save_depth:
+        import numpy as np
+        os.makedirs(args.save_depth, exist_ok=True)
+        depth_avg, mask, _ = acc.geometric(return_points=False, **geo_kwargs)
+        depth_avg, mask = depth_avg.cpu().numpy(), mask.cpu().numpy().astype(np.float32)
+        for v in range(len(dataset)):
+            io.write_pfm(os.path.join(args.save_depth, "%08d_geo.pfm" % v), depth_avg[v])
+            io.write_pfm(os.path.join(args.save_depth, "%08d_geo_mask.pfm" % v), mask[v])
+        out["kept_share_per_view_geo"] = [float(m.mean()) for m in mask]
     if args.gt:
         kw = {}
         if args.obs_mask:
