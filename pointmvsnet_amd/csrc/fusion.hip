@@ -14,29 +14,17 @@
 //                  only read and used[other] only written (always 1) by a launch, so thread order cannot matter.
 //   fuse_compact   ordered compaction: the host's inclusive prefix sum of the emit mask gives every emitting pixel its
 //                  row; view-major, then row-major.  No atomics anywhere.
-#include "pf_common.h"
+// The layout of view_maps and pair_maps, the tiling and the map itself: pf_camera.h.
+#include "pf_camera.h"
 
 namespace {
 
-constexpr int kTile = 16;
-
-// view_maps (V, PF_FUSE_VIEW_FLOATS): A = R^-1 K^-1 (row-major 3x3), then C = -R^-1 t:  X = (A (x+.5, y+.5, 1)) d + C
-// pair_maps (V, V, PF_FUSE_PAIR_FLOATS), entry [i][j]: M = K_j R_j R_i^-1 K_i^-1 (3x3), T = K_j (t_j - R_j R_i^-1 t_i),
-//   fb = K_j[0][0] |C_i - C_j|:  q = (M (x+.5, y+.5, 1)) d + T
-__device__ __forceinline__ void back_project(const float* __restrict__ a, float px, float py, float d, float& X, float& Y,
-                                             float& Z) {
-  X = (a[0] * px + a[1] * py + a[2]) * d + a[9];
-  Y = (a[3] * px + a[4] * py + a[5]) * d + a[10];
-  Z = (a[6] * px + a[7] * py + a[8]) * d + a[11];
-}
-
-__global__ __launch_bounds__(kTile * kTile) void fuse_stage_a_kernel(
+__global__ __launch_bounds__(kPfTile * kPfTile) void fuse_stage_a_kernel(
     const float* __restrict__ depth, const unsigned char* __restrict__ colour, const float* __restrict__ view_maps,
     const float* __restrict__ pair_maps, int V, int h, int w, float disp_threshold, float depth_min, float depth_max,
     int* __restrict__ count, float* __restrict__ point, unsigned char* __restrict__ colour_out, int* __restrict__ match) {
-  const int x = blockIdx.x * kTile + (threadIdx.x & (kTile - 1));
-  const int y = blockIdx.y * kTile + (threadIdx.x / kTile);
-  const int i = blockIdx.z;
+  int x, y, i;
+  pf_tile_pixel(x, y, i);
   if (x >= w || y >= h) return;
   const int hw = h * w;
   const int p = y * w + x;
@@ -46,7 +34,7 @@ __global__ __launch_bounds__(kTile * kTile) void fuse_stage_a_kernel(
   const float px = (float)x + 0.5f, py = (float)y + 0.5f;
   float sx = 0.0f, sy = 0.0f, sz = 0.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
   if (valid) {
-    back_project(view_maps + i * PF_FUSE_VIEW_FLOATS, px, py, d, sx, sy, sz);
+    pf_apply_map(view_maps + i * PF_FUSE_VIEW_FLOATS, px, py, d, sx, sy, sz);
     if (colour != nullptr) {
       cr = (float)colour[ip * 3 + 0];
       cg = (float)colour[ip * 3 + 1];
@@ -57,9 +45,8 @@ __global__ __launch_bounds__(kTile * kTile) void fuse_stage_a_kernel(
   for (int j = 0; j < V; ++j) {
     if (j == i) continue;
     const float* __restrict__ m = pair_maps + ((int64_t)i * V + j) * PF_FUSE_PAIR_FLOATS;
-    const float qx = (m[0] * px + m[1] * py + m[2]) * d + m[9];
-    const float qy = (m[3] * px + m[4] * py + m[5]) * d + m[10];
-    const float z = (m[6] * px + m[7] * py + m[8]) * d + m[11];
+    float qx, qy, z;
+    pf_apply_map(m, px, py, d, qx, qy, z);
     const float u = qx / z, v = qy / z;
     // floor(u) in [0, w) <=> 0 <= u < w; the comparisons are false for NaN, so the conversions below are in range
     const bool inside = valid && z > 0.0f && u >= 0.0f && u < (float)w && v >= 0.0f && v < (float)h;
@@ -73,7 +60,7 @@ __global__ __launch_bounds__(kTile * kTile) void fuse_stage_a_kernel(
     ++slot;
     if (consistent) {
       float X, Y, Z;
-      back_project(view_maps + j * PF_FUSE_VIEW_FLOATS, (float)xj + 0.5f, (float)yj + 0.5f, dj, X, Y, Z);
+      pf_apply_map(view_maps + j * PF_FUSE_VIEW_FLOATS, (float)xj + 0.5f, (float)yj + 0.5f, dj, X, Y, Z);
       sx += X;
       sy += Y;
       sz += Z;
@@ -137,12 +124,12 @@ int pf_fuse_stage_a_f32(const float* depth, const unsigned char* colour, const f
                         int V, int h, int w, float disp_threshold, float depth_min, float depth_max, int* count,
                         float* point, unsigned char* colour_out, int* match, void* stream) {
   PF_REQUIRE(V >= 1 && h >= 0 && w >= 0 && (int64_t)h * w <= INT32_MAX / 4);
-  PF_REQUIRE((pf_cdiv(h, kTile) <= 65535) && V <= 65535);
+  PF_REQUIRE((pf_cdiv(h, kPfTile) <= 65535) && V <= 65535);
   if (h == 0 || w == 0) return PF_OK;
   PF_REQUIRE(depth && view_maps && pair_maps && count && point && (match || V == 1));
   PF_REQUIRE((colour == nullptr) == (colour_out == nullptr));
-  hipLaunchKernelGGL(fuse_stage_a_kernel, dim3((unsigned)pf_cdiv(w, kTile), (unsigned)pf_cdiv(h, kTile), (unsigned)V),
-                     dim3(kTile * kTile), 0, (hipStream_t)stream, depth, colour, view_maps, pair_maps, V, h, w,
+  hipLaunchKernelGGL(fuse_stage_a_kernel, dim3((unsigned)pf_cdiv(w, kPfTile), (unsigned)pf_cdiv(h, kPfTile), (unsigned)V),
+                     dim3(kPfTile * kPfTile), 0, (hipStream_t)stream, depth, colour, view_maps, pair_maps, V, h, w,
                      disp_threshold, depth_min, depth_max, count, point, colour_out, match);
   return pf_launch_status();
 }

@@ -11,20 +11,18 @@
 //                source.  No match array, no LDS, no scratch, no atomics: per pixel 4 bytes in, 4 M gathers of 4 bytes,
 //                21 bytes out.
 // The ordered compaction of the masked points is pf_fuse_compact_f32 (fusion.hip) behind the host's prefix sum.
-#include "pf_common.h"
+// The layout of view_maps and of a pair row, the tiling and the map itself: pf_camera.h.
+#include "pf_camera.h"
 
 namespace {
 
-constexpr int kGeoTile = 16;
-
-__global__ __launch_bounds__(kGeoTile * kGeoTile) void geo_filter_kernel(
+__global__ __launch_bounds__(kPfTile * kPfTile) void geo_filter_kernel(
     const float* __restrict__ depth, const float* __restrict__ view_maps, const int* __restrict__ sources,
     const float* __restrict__ pair_maps, int V, int M, int h, int w, float pix_threshold, float rel_depth_threshold,
     int num_consistent, float depth_min, float depth_max, int* __restrict__ count, float* __restrict__ depth_avg,
     float* __restrict__ point, unsigned char* __restrict__ emit) {
-  const int x = blockIdx.x * kGeoTile + (threadIdx.x & (kGeoTile - 1));
-  const int y = blockIdx.y * kGeoTile + (threadIdx.x / kGeoTile);
-  const int i = blockIdx.z;
+  int x, y, i;
+  pf_tile_pixel(x, y, i);
   if (x >= w || y >= h) return;
   const int hw = h * w;
   const int64_t ip = (int64_t)i * hw + y * w + x;
@@ -39,9 +37,8 @@ __global__ __launch_bounds__(kGeoTile * kGeoTile) void geo_filter_kernel(
     if (j < 0 || j >= V || j == i) continue;           // wave-uniform: a pad, or the view itself
     const float* __restrict__ f = pair_maps + ((int64_t)i * M + m) * (2 * PF_FUSE_PAIR_FLOATS);   // i -> j
     const float* __restrict__ b = f + PF_FUSE_PAIR_FLOATS;                                         // j -> i
-    const float qx = (f[0] * px + f[1] * py + f[2]) * d + f[9];
-    const float qy = (f[3] * px + f[4] * py + f[5]) * d + f[10];
-    const float z = (f[6] * px + f[7] * py + f[8]) * d + f[11];
+    float qx, qy, z;
+    pf_apply_map(f, px, py, d, qx, qy, z);
     const float u = qx / z, v = qy / z;
     const float fx = u - 0.5f, fy = v - 0.5f;
     const float x0 = floorf(fx), y0 = floorf(fy);
@@ -59,9 +56,8 @@ __global__ __launch_bounds__(kGeoTile * kGeoTile) void geo_filter_kernel(
     const float top = t00 * (1.0f - wx) + t01 * wx;
     const float bot = t10 * (1.0f - wx) + t11 * wx;
     const float ds = top * (1.0f - wy) + bot * wy;
-    const float rx = (b[0] * u + b[1] * v + b[2]) * ds + b[9];
-    const float ry = (b[3] * u + b[4] * v + b[5]) * ds + b[10];
-    const float dr = (b[6] * u + b[7] * v + b[8]) * ds + b[11];
+    float rx, ry, dr;
+    pf_apply_map(b, u, v, ds, rx, ry, dr);
     const float ex = rx / dr - px, ey = ry / dr - py;
     const bool consistent = readable && dr > 0.0f && sqrtf(ex * ex + ey * ey) < pix_threshold &&
                             fabsf(dr - d) / d < rel_depth_threshold;
@@ -72,12 +68,13 @@ __global__ __launch_bounds__(kGeoTile * kGeoTile) void geo_filter_kernel(
   }
   const bool keep = valid && n >= num_consistent;
   const float avg = keep ? sum / (float)(n + 1) : 0.0f;
-  const float* __restrict__ a = view_maps + i * PF_FUSE_VIEW_FLOATS;
+  float X, Y, Z;
+  pf_apply_map(view_maps + i * PF_FUSE_VIEW_FLOATS, px, py, avg, X, Y, Z);
   count[ip] = n;                                        // 0 without a depth of its own: `inside` asks for it
   depth_avg[ip] = avg;
-  point[ip * 3 + 0] = keep ? (a[0] * px + a[1] * py + a[2]) * avg + a[9] : 0.0f;
-  point[ip * 3 + 1] = keep ? (a[3] * px + a[4] * py + a[5]) * avg + a[10] : 0.0f;
-  point[ip * 3 + 2] = keep ? (a[6] * px + a[7] * py + a[8]) * avg + a[11] : 0.0f;
+  point[ip * 3 + 0] = keep ? X : 0.0f;
+  point[ip * 3 + 1] = keep ? Y : 0.0f;
+  point[ip * 3 + 2] = keep ? Z : 0.0f;
   emit[ip] = keep ? 1 : 0;
 }
 
@@ -89,11 +86,11 @@ int pf_geo_filter_f32(const float* depth, const float* view_maps, const int* sou
                       int h, int w, float pix_threshold, float rel_depth_threshold, int num_consistent, float depth_min,
                       float depth_max, int* count, float* depth_avg, float* point, unsigned char* emit, void* stream) {
   PF_REQUIRE(V >= 1 && M >= 0 && h >= 0 && w >= 0 && (int64_t)h * w <= INT32_MAX / 4);
-  PF_REQUIRE((pf_cdiv(h, kGeoTile) <= 65535) && V <= 65535);
+  PF_REQUIRE((pf_cdiv(h, kPfTile) <= 65535) && V <= 65535);
   if (h == 0 || w == 0) return PF_OK;
   PF_REQUIRE(depth && view_maps && count && depth_avg && point && emit && ((sources && pair_maps) || M == 0));
-  hipLaunchKernelGGL(geo_filter_kernel, dim3((unsigned)pf_cdiv(w, kGeoTile), (unsigned)pf_cdiv(h, kGeoTile), (unsigned)V),
-                     dim3(kGeoTile * kGeoTile), 0, (hipStream_t)stream, depth, view_maps, sources, pair_maps, V, M, h, w,
+  hipLaunchKernelGGL(geo_filter_kernel, dim3((unsigned)pf_cdiv(w, kPfTile), (unsigned)pf_cdiv(h, kPfTile), (unsigned)V),
+                     dim3(kPfTile * kPfTile), 0, (hipStream_t)stream, depth, view_maps, sources, pair_maps, V, M, h, w,
                      pix_threshold, rel_depth_threshold, num_consistent, depth_min, depth_max, count, depth_avg, point,
                      emit);
   return pf_launch_status();

@@ -35,40 +35,22 @@ import os.path as osp
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, camera_maps as cm
+from .camera_maps import PAIR_FLOATS, VIEW_FLOATS  # noqa: F401
 from .utils.io import load_cam_dtu, load_pfm, write_ply
-
-VIEW_FLOATS = 12       # PF_FUSE_VIEW_FLOATS of include/pointflow_hip.h
-PAIR_FLOATS = 16       # PF_FUSE_PAIR_FLOATS
-
-
-def _host_f64(a):
-    if isinstance(a, torch.Tensor):
-        a = a.detach().cpu().numpy()
-    return np.asarray(a, dtype=np.float64)
-
 
 def camera_maps(intrinsics, extrinsics):
     """``(view_maps (V, 12), pair_maps (V, V, 16))`` float32 arrays in the layout of ``pf_fuse_stage_a_f32``, composed in
     float64 from ``intrinsics`` (V, 3, 3) and ``extrinsics`` (V, 3, 4) or (V, 4, 4) (world -> camera)."""
-    K = _host_f64(intrinsics)
-    E = _host_f64(extrinsics)
-    if K.ndim != 3 or K.shape[1:] != (3, 3) or E.ndim != 3 or E.shape[0] != K.shape[0] or E.shape[1:] not in ((3, 4), (4, 4)):
-        raise ValueError("fuse_depth_maps: intrinsics must be (V, 3, 3) and extrinsics (V, 3, 4) or (V, 4, 4)")
-    V = K.shape[0]
-    R, t = E[:, :3, :3], E[:, :3, 3]
-    Rinv = np.linalg.inv(R)
-    A = Rinv @ np.linalg.inv(K)
-    C = -np.einsum("vab,vb->va", Rinv, t)
-    view_maps = np.concatenate([A.reshape(V, 9), C], axis=1)
+    return _maps_of(cm.decompose("fuse_depth_maps", intrinsics, extrinsics))
+
+
+def _maps_of(cams):
+    V = cams[0].shape[0]
     pair_maps = np.zeros((V, V, PAIR_FLOATS))
-    for i in range(V):
-        for j in range(V):
-            KR = K[j] @ R[j]
-            pair_maps[i, j, :9] = (KR @ A[i]).reshape(9)
-            pair_maps[i, j, 9:12] = KR @ C[i] + K[j] @ t[j]
-            pair_maps[i, j, 12] = K[j, 0, 0] * np.linalg.norm(C[i] - C[j])
-    return view_maps.astype(np.float32), pair_maps.astype(np.float32)
+    for i, j in np.ndindex(V, V):
+        cm.pair_row(cams, i, j, pair_maps[i, j], with_fb=True)
+    return cm.view_maps(cams), pair_maps.astype(np.float32)
 
 
 def fuse_depth_maps(depths, intrinsics, extrinsics, images=None, disp_threshold=0.12, num_consistent=3, depth_min=1e-3,
@@ -81,30 +63,10 @@ def fuse_depth_maps(depths, intrinsics, extrinsics, images=None, disp_threshold=
     ``return_stages`` a third value, the dict of the Stage A tensors ``count`` (V, h, w) int32, ``point`` (V, h, w, 3),
     ``colour`` (V, h, w, 3) or None, ``match`` (V, V-1, h, w) int32 and the Stage B mask ``emit`` (V, h, w) bool.
     There is no CPU path."""
-    if not isinstance(depths, torch.Tensor):
-        depths = list(depths)
-        if len(set(tuple(d.shape) for d in depths)) > 1:
-            raise ValueError("fuse_depth_maps: the depth maps have different sizes")
-        depths = torch.stack([torch.as_tensor(d) for d in depths])
-    if depths.dim() != 3:
-        raise ValueError("fuse_depth_maps: depths must be (V, h, w)")
-    if int(num_consistent) < 1:
-        raise ValueError("fuse_depth_maps: num_consistent must be at least 1")
-    _lib.require_gpu(depths, images if isinstance(images, torch.Tensor) else None)
-    dev = depths.device
-    V, h, w = (int(s) for s in depths.shape)
-    view_np, pair_np = camera_maps(intrinsics, extrinsics)
-    if view_np.shape[0] != V:
-        raise ValueError("fuse_depth_maps: %d depth maps but %d cameras" % (V, view_np.shape[0]))
-    depths = depths.contiguous().float()
-    if images is not None:
-        images = torch.as_tensor(images).to(dev)
-        if tuple(images.shape) != (V, h, w, 3) or images.dtype != torch.uint8:
-            raise ValueError("fuse_depth_maps: images must be (V, h, w, 3) uint8 of the depth maps' size")
-        images = images.contiguous()
+    depths, images, V, h, w, dev = cm.normalise_inputs("fuse_depth_maps", depths, images, num_consistent)
+    maps = _maps_of(cm.decompose("fuse_depth_maps", intrinsics, extrinsics, V))
     with _lib.on_device(dev):
-        view_maps = torch.from_numpy(view_np).to(dev)
-        pair_maps = torch.from_numpy(pair_np).to(dev)
+        view_maps, pair_maps = (torch.from_numpy(a).to(dev) for a in maps)
         count = torch.empty((V, h, w), dtype=torch.int32, device=dev)
         point = torch.empty((V, h, w, 3), dtype=torch.float32, device=dev)
         colour = torch.empty((V, h, w, 3), dtype=torch.uint8, device=dev) if images is not None else None
@@ -119,13 +81,7 @@ def fuse_depth_maps(depths, intrinsics, extrinsics, images=None, disp_threshold=
         for i in range(V):
             _lib.call("pf_fuse_mark", _lib.ptr(count), _lib.ptr(match), _lib.ptr(used), _lib.ptr(emit), V, i, h, w,
                       int(num_consistent), _lib.stream())
-        # the offsets are plumbing (an int64 prefix sum of the mask); the ordered scatter is ours
-        rank = torch.cumsum(emit.view(-1), dim=0, dtype=torch.int64)
-        rows = int(rank[-1]) if rank.numel() else 0
-        points = torch.empty((rows, 3), dtype=torch.float32, device=dev)
-        colours = torch.empty((rows, 3), dtype=torch.uint8, device=dev) if images is not None else None
-        _lib.call("pf_fuse_compact_f32", _lib.ptr(emit), _lib.ptr(rank), _lib.ptr(point), _lib.ptr(colour), V * h * w, rows,
-                  _lib.ptr(points), _lib.ptr(colours), _lib.stream())
+        points, colours = cm.compact(emit, point, colour)
     if not return_stages:
         return points, colours
     return points, colours, {"count": count, "point": point, "colour": colour, "match": match, "emit": emit.bool()}

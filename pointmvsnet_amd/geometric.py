@@ -52,8 +52,7 @@ listed pairs are composed, so cost and memory are linear in the number of views.
 import numpy as np
 import torch
 
-from . import _lib
-from .fusion import PAIR_FLOATS, _host_f64
+from . import _lib, camera_maps as cm
 
 _WHO = "geometric_filter"
 
@@ -82,35 +81,23 @@ def sources_from_pairs(pair_list, view_num, num_src):
 
 def view_maps_of(intrinsics, extrinsics):
     """``view_maps (V, 12)`` float32 of ``fusion.camera_maps`` alone (that function also composes all V x V pairs)."""
-    K = _host_f64(intrinsics)
-    E = _host_f64(extrinsics)
-    Rinv = np.linalg.inv(E[:, :3, :3])
-    A = Rinv @ np.linalg.inv(K)
-    C = -np.einsum("vab,vb->va", Rinv, E[:, :3, 3])
-    return np.concatenate([A.reshape(K.shape[0], 9), C], axis=1).astype(np.float32)
+    return cm.view_maps(cm.decompose("view_maps_of", intrinsics, extrinsics))
 
 
 def source_maps(intrinsics, extrinsics, sources):
     """``pair_maps (V, M, 2, 16)`` float32 of ``pf_geo_filter_f32`` for the ``(V, M)`` table ``sources``, composed in
     float64: entry ``[i, m, 0]`` is ``fusion.camera_maps``' ``i -> j`` layout for ``j = sources[i, m]``, ``[i, m, 1]`` the
     ``j -> i`` one (the disparity scale ``fb`` is left 0: nothing reads it); pads and ``j == i`` stay 0."""
-    K = _host_f64(intrinsics)
-    E = _host_f64(extrinsics)
-    V, M = sources.shape
-    R, t = E[:, :3, :3], E[:, :3, 3]
-    Rinv = np.linalg.inv(R)
-    A = Rinv @ np.linalg.inv(K)
-    C = -np.einsum("vab,vb->va", Rinv, t)
-    out = np.zeros((V, M, 2, PAIR_FLOATS))
-    for i in range(V):
-        for m in range(M):
-            j = int(sources[i, m])
-            if j < 0 or j == i:
-                continue
-            for slot, (a, b) in enumerate(((i, j), (j, i))):
-                KR = K[b] @ R[b]
-                out[i, m, slot, :9] = (KR @ A[a]).reshape(9)
-                out[i, m, slot, 9:12] = KR @ C[a] + K[b] @ t[b]
+    return _source_maps(cm.decompose("source_maps", intrinsics, extrinsics), sources)
+
+
+def _source_maps(cams, sources):
+    out = np.zeros(sources.shape + (2, cm.PAIR_FLOATS))
+    for i, m in np.ndindex(*sources.shape):
+        j = int(sources[i, m])
+        if j >= 0 and j != i:
+            cm.pair_row(cams, i, j, out[i, m, 0])
+            cm.pair_row(cams, j, i, out[i, m, 1])
     return out.astype(np.float32)
 
 
@@ -141,37 +128,13 @@ def geometric_filter(depths, intrinsics, extrinsics, images=None, sources=None, 
     also ``(points (N, 3) float32, colours (N, 3) uint8 or None)``: five values; with ``return_stages`` last the dict of
     the kernel's per-pixel ``point`` (V, h, w, 3) and ``emit`` (V, h, w) uint8.  Everything is on the device of ``depths``.
     There is no CPU path."""
-    if not isinstance(depths, torch.Tensor):
-        depths = list(depths)
-        if len(set(tuple(d.shape) for d in depths)) > 1:
-            raise ValueError("%s: the depth maps have different sizes" % _WHO)
-        depths = torch.stack([torch.as_tensor(d) for d in depths])
-    if depths.dim() != 3:
-        raise ValueError("%s: depths must be (V, h, w)" % _WHO)
-    if int(num_consistent) < 1:
-        raise ValueError("%s: num_consistent must be at least 1" % _WHO)
-    V, h, w = (int(s) for s in depths.shape)
-    table = _source_table(sources, V)
-    _lib.require_gpu(depths, images if isinstance(images, torch.Tensor) else None)
-    dev = depths.device
-    K, E = _host_f64(intrinsics), _host_f64(extrinsics)
-    if K.ndim != 3 or K.shape[1:] != (3, 3) or E.ndim != 3 or E.shape[0] != K.shape[0] or E.shape[1:] not in ((3, 4), (4, 4)):
-        raise ValueError("%s: intrinsics must be (V, 3, 3) and extrinsics (V, 3, 4) or (V, 4, 4)" % _WHO)
-    if K.shape[0] != V:
-        raise ValueError("%s: %d depth maps but %d cameras" % (_WHO, V, K.shape[0]))
-    M = int(table.shape[1])
-    view_np = view_maps_of(K, E)
-    pair_np = source_maps(K, E, table)
-    depths = depths.contiguous().float()
-    if images is not None:
-        images = torch.as_tensor(images).to(dev)
-        if tuple(images.shape) != (V, h, w, 3) or images.dtype != torch.uint8:
-            raise ValueError("%s: images must be (V, h, w, 3) uint8 of the depth maps' size" % _WHO)
-        images = images.contiguous()
+    depths = cm.stack_depths(_WHO, depths, num_consistent)
+    table = _source_table(sources, int(depths.shape[0]))               # a bad table is reported before a missing GPU
+    depths, images, V, h, w, dev = cm.normalise_inputs(_WHO, depths, images, num_consistent)
+    cams = cm.decompose(_WHO, intrinsics, extrinsics, V)
+    maps, M = (cm.view_maps(cams), table, _source_maps(cams, table)), int(table.shape[1])
     with _lib.on_device(dev):
-        view_maps = torch.from_numpy(view_np).to(dev)
-        src = torch.from_numpy(table).to(dev)
-        pair_maps = torch.from_numpy(pair_np).to(dev)
+        view_maps, src, pair_maps = (torch.from_numpy(a).to(dev) for a in maps)
         count = torch.empty((V, h, w), dtype=torch.int32, device=dev)
         depth_avg = torch.empty((V, h, w), dtype=torch.float32, device=dev)
         point = torch.empty((V, h, w, 3), dtype=torch.float32, device=dev)
@@ -184,13 +147,4 @@ def geometric_filter(depths, intrinsics, extrinsics, images=None, sources=None, 
                   _lib.ptr(count), _lib.ptr(depth_avg), _lib.ptr(point), _lib.ptr(emit), _lib.stream(), algo_bytes=algo)
         out = (depth_avg, emit.bool(), count)
         stages = ({"point": point, "emit": emit},) if return_stages else ()
-        if not return_points:
-            return out + stages
-        # the offsets are plumbing (an int64 prefix sum of the mask); the ordered scatter is fusion.hip's
-        rank = torch.cumsum(emit.view(-1), dim=0, dtype=torch.int64)
-        rows = int(rank[-1]) if rank.numel() else 0
-        points = torch.empty((rows, 3), dtype=torch.float32, device=dev)
-        colours = torch.empty((rows, 3), dtype=torch.uint8, device=dev) if images is not None else None
-        _lib.call("pf_fuse_compact_f32", _lib.ptr(emit), _lib.ptr(rank), _lib.ptr(point), _lib.ptr(images), V * h * w, rows,
-                  _lib.ptr(points), _lib.ptr(colours), _lib.stream())
-    return out + (points, colours) + stages
+        return out + (cm.compact(emit, point, images) if return_points else ()) + stages

@@ -343,6 +343,34 @@ def test_source_maps_reproduce_both_projections():
     assert np.array_equal(geometric.view_maps_of(K, E), fusion.camera_maps(K, E)[0])
 
 
+def test_source_maps_are_the_pair_maps_of_the_fusion():
+    """One composition serves both fusers: a listed pair's two rows are, byte for byte, the ``i -> j`` and ``j -> i``
+    entries of ``fusion.camera_maps`` without the disparity scale; pads and a row naming itself stay zero."""
+    from pointmvsnet_amd import fusion, geometric
+    for scene, tables in ((make_plane_scene(V5), (None, TABLE)), (make_plane_scene(3, h=SMALL[0], w=SMALL[1]), (None, TABLE[:3] % 3))):
+        _, K, E, _, _ = scene
+        V = K.shape[0]
+        view, pair = fusion.camera_maps(K, E)
+        assert geometric.view_maps_of(K, E).tobytes() == view.tobytes()
+        for table in tables:
+            if table is None:
+                table = np.array([[j for j in range(V) if j != i] for i in range(V)])
+            src = geometric.source_maps(K, E, table)
+            assert src.dtype == np.float32 and src.shape == table.shape + (2, fusion.PAIR_FLOATS)
+            assert not src[..., 12:].any()
+            listed = 0
+            for i in range(V):
+                for m, j in enumerate(table[i]):
+                    if j < 0 or j == i:
+                        assert not src[i, m].any()
+                        continue
+                    listed += 1
+                    assert src[i, m, 0, :12].tobytes() == pair[i, j, :12].tobytes()
+                    assert src[i, m, 1, :12].tobytes() == pair[j, i, :12].tobytes()
+                    assert src[i, m, 0, :12].any() and pair[i, j, 12] > 0
+            assert listed == int(((table >= 0) & (table != np.arange(V)[:, None])).sum()) > 0
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # 2. GPU
 # ---------------------------------------------------------------------------------------------------------------------
