@@ -13,9 +13,9 @@ Two execution paths:
 * training (autograd): the reference's composition on the differentiable HIP operators
   (``FeatureFetcher``, ``gather_knn``) and stock ATen for the rest, so gradients match the reference.
 
-Camera algebra (3x3 inverses, intrinsic scaling) is done once per forward on the host in float32 with
-the same ATen CPU calls the reference makes (model.py:54-61, :159-170) and uploaded as small constant
-blocks; it is microseconds of work and keeps the geometry bit-identical to the reference's.
+Camera algebra (3x3 inverses, intrinsic scaling) is done once per forward on the host in float32, bit-identical
+to the ATen CPU calls the reference makes (model.py:54-61, :159-170; ``_Cameras`` states them), and uploaded as
+one constant block (``ScenePlan`` / ``TrainPlan``); it is microseconds of work.
 """
 import collections
 import os
@@ -75,8 +75,18 @@ def _host_cams(data_batch):
     return cams.float()
 
 
+def _host_stats(data_batch):
+    """Host float32 copies of the image normalisation's ``mean`` and ``std``; ``mean_host`` / ``std_host`` (optional)
+    spare the D2H copy + sync."""
+    mean = data_batch["mean_host"] if "mean_host" in data_batch else data_batch["mean"].detach().cpu()
+    std = data_batch["std_host"] if "std_host" in data_batch else data_batch["std"].detach().cpu()
+    return mean.float(), std.float()
+
+
 class _Cameras(object):
-    """Host-side (float32, ATen-CPU) camera algebra shared by both paths."""
+    """Host-side camera algebra in the reference's own form: its float32 ATen-CPU calls (model.py:54-61, :159-170).
+    The product computes the same values in ``_PlanBlock.fill_host_`` and does not call this class; it is the
+    statement the tests (test_host.py, test_gpu_teacher.py, test_gpu_stages.py) compare the plans and stages against."""
 
     def __init__(self, cams_host, is_test):
         self.ext = cams_host[:, :, 0, :3, :4].clone()                       # (B,V,3,4)
@@ -117,34 +127,26 @@ class _Cameras(object):
         return torch.stack(rows).float().contiguous()
 
 
-class ScenePlan(object):
+class _PlanBlock(object):
     """Every host-derived constant of one forward, in ONE pinned host block mirrored by ONE device block.
 
-    ``update_(data_batch)`` redoes the camera algebra on the host (same ATen-CPU calls as the reference)
-    and refreshes the device block with a single asynchronous copy; ``PointMVSNet.run(plan, imgs)`` then
-    touches the device only.  That split is what makes the whole forward capturable in a hipGraph and
-    replayable on a new scene (pointmvsnet_amd/graph.py), and it replaces ~45 tiny pageable H2D copies per
-    depth map by one."""
+    ``update_(data_batch)`` redoes the camera algebra on the host (``fill_host_``) and refreshes the device block
+    with a single asynchronous copy; the forward then touches the device only -- no per-call H2D copies, no
+    ``.cpu()`` round trip.  That split is what makes a whole pass capturable in a hipGraph and replayable on the next
+    scene, and it replaces ~45 tiny pageable H2D copies per depth map by one.  ``ScenePlan`` and ``TrainPlan`` are
+    this block with their own entry table (name, shape), ``matches`` key and name in the error message."""
 
-    def __init__(self, device, B, V, H, W, img_scales, inter_scales, is_test, num_depth):
-        self.device, self.B, self.V, self.H, self.W = device, B, V, H, W
+    def __init__(self, device, B, V, num_depth, img_scales, inter_scales, is_test, entries):
+        self.device, self.B, self.V, self.D = device, B, V, int(num_depth)
         self.img_scales, self.inter_scales = tuple(img_scales), tuple(inter_scales)
-        self.is_test, self.D = bool(is_test), int(num_depth)
-        for s in self.img_scales:
-            if is_test and s not in (0.125, 0.25, 0.5, 1.0):
-                raise NotImplementedError
-        P = 27 + 21 * V + 1
-        self._layout = {}
-        off = 0
-        for name, shape in [("K_coarse", (B, V, 3, 3)), ("ext", (B, V, 3, 4)), ("Kinv0", (B, 1, 3, 3)),
-                            ("Rinv0", (B, 1, 3, 3)), ("t0", (B, 1, 3, 1)), ("depths", (B, self.D)),
-                            ("sa_params", (B, 3))] + [("pack%d" % i, (B, P)) for i in range(len(self.img_scales))]:
+        self.is_test = bool(is_test)
+        self._layout, off = {}, 0
+        for name, shape in entries:
             n = 1
             for d in shape:
                 n *= d
-            n_pad = (n + 3) // 4 * 4                       # keep every slice 16-byte aligned
             self._layout[name] = (off, n, shape)
-            off += n_pad
+            off += (n + 3) // 4 * 4                        # keep every slice 16-byte aligned
         self.host = torch.zeros(off, dtype=torch.float32)
         if torch.cuda.is_available():
             self.host = self.host.pin_memory()
@@ -160,15 +162,14 @@ class ScenePlan(object):
         off, n, shape = self._layout[name]
         return self.dev[off:off + n].view(shape)
 
-    def matches(self, device, B, V, H, W, img_scales, inter_scales, is_test, num_depth):
-        return (self.device == device and (self.B, self.V, self.H, self.W) == (B, V, H, W)
+    def _same(self, device, B, V, num_depth, img_scales, inter_scales, is_test):
+        return (self.device == device and (self.B, self.V, self.D) == (B, V, int(num_depth))
                 and self.img_scales == tuple(img_scales) and self.inter_scales == tuple(inter_scales)
-                and self.is_test == bool(is_test) and self.D == int(num_depth))
+                and self.is_test == bool(is_test))
 
     def update_(self, data_batch):
         """Host algebra into the pinned block, then one asynchronous H2D on the current stream."""
-        self.fill_host_(data_batch)
-        return self.upload_()
+        return self.fill_host_(data_batch).upload_()
 
     def upload_(self):
         self.dev.copy_(self.host, non_blocking=True)
@@ -179,7 +180,8 @@ class ScenePlan(object):
 
     def fill_host_(self, data_batch):
         """Only the host half: redo the camera algebra into the pinned block (a captured graph that contains the
-        H2D copy as its first node reads it at replay time; see graph.GraphedForward).
+        H2D copy as its first node reads it at replay time; see graph.GraphedForward).  Fills every entry the plan
+        declares; the names of the other plan's table are skipped.
 
         The values are ``_Cameras``' (the reference's float32 ATen-CPU arithmetic, model.py:54-61, :159-170), bit for
         bit (tests/test_host.py): the 3x3 inverses are the same LAPACK calls on matrices of the same memory layout
@@ -192,11 +194,10 @@ class ScenePlan(object):
         B, V, D = self.B, self.V, self.D
         cams = cams_t.numpy()
         if int(cams[0, 0, 1, 3, 2]) != D:
-            raise RuntimeError("ScenePlan: num_depth changed (%d -> %d); build a new plan" % (D, int(cams[0, 0, 1, 3, 2])))
-        mean_h = data_batch["mean_host"] if "mean_host" in data_batch else data_batch["mean"].detach().cpu()
-        std_h = data_batch["std_host"] if "std_host" in data_batch else data_batch["std"].detach().cpu()
-        mean_h = mean_h.float().numpy().reshape(B, 3)
-        std_h = std_h.float().numpy().reshape(B, 3)
+            raise RuntimeError("%s: num_depth changed (%d -> %d); build a new plan"
+                               % (type(self).__name__, D, int(cams[0, 0, 1, 3, 2])))
+        mean_h, std_h = _host_stats(data_batch)
+        mean_h, std_h = mean_h.numpy().reshape(B, 3), std_h.numpy().reshape(B, 3)
         f32 = np.float32
         ext = np.ascontiguousarray(cams[:, :, 0, :3, :4])                   # (B,V,3,4), like _Cameras.ext
         K_raw = cams[:, :, 1, :3, :3]
@@ -227,8 +228,9 @@ class ScenePlan(object):
         hb, lay = self._host_np, self._layout
 
         def put(name, arr):
-            off, n, _ = lay[name]
-            hb[off:off + n] = arr.reshape(-1)
+            if name in lay:
+                off, n, _ = lay[name]
+                hb[off:off + n] = arr.reshape(-1)
 
         put("K_coarse", K_coarse)
         put("ext", ext)
@@ -238,11 +240,18 @@ class ScenePlan(object):
         off, n, _ = lay["depths"]
         for b in range(B):
             torch.linspace(float(start[b]), float(end[b]), D, out=self.host[off + b * D:off + (b + 1) * D])
+        put("d_start", start)
+        put("d_int", interval)
+        put("mean", mean_h)
+        put("std", std_h)
         put("sa_params", np.stack([start, end, interval], axis=1))
         P = 27 + 21 * V + 1
         for i, inter in enumerate(self.inter_scales):
-            off, n, _ = lay["pack%d" % i]
             step = f32(inter) * interval                                    # (B,) hypothesis spacing of iteration i
+            put("interval%d" % i, step)
+            put("K_flow%d" % i, K_flow[i])
+            put("Kinv_flow%d" % i, Kinv_flow[i])
+            off, n, _ = lay["pack%d" % i]
             for b in range(B):
                 row = hb[off + b * P:off + (b + 1) * P]
                 row[0:9] = Kinv_flow[i][b].reshape(-1)
@@ -257,86 +266,37 @@ class ScenePlan(object):
         return self
 
 
-class TrainPlan(object):
-    """The host-derived constants of one forward of the AUTOGRAD path (reference model.py:45-305), in one pinned
-    host block mirrored by one device block -- ScenePlan's idea for the training step: the forward touches device
-    tensors only (no per-call H2D copies, no ``.cpu()`` round trip for the flow intrinsics), so forward + loss +
-    backward can be captured in a hipGraph and replayed on the next scene (train_step.GraphedTrainStep)."""
+class ScenePlan(_PlanBlock):
+    """The constants of the fused inference route, ``PointMVSNet.run(plan, imgs)`` (graph.GraphedForward)."""
+
+    def __init__(self, device, B, V, H, W, img_scales, inter_scales, is_test, num_depth):
+        for s in img_scales:
+            if is_test and s not in (0.125, 0.25, 0.5, 1.0):
+                raise NotImplementedError
+        self.H, self.W = H, W
+        _PlanBlock.__init__(self, device, B, V, num_depth, img_scales, inter_scales, is_test, [
+            ("K_coarse", (B, V, 3, 3)), ("ext", (B, V, 3, 4)), ("Kinv0", (B, 1, 3, 3)), ("Rinv0", (B, 1, 3, 3)),
+            ("t0", (B, 1, 3, 1)), ("depths", (B, int(num_depth))), ("sa_params", (B, 3))]
+            + [("pack%d" % i, (B, 27 + 21 * V + 1)) for i in range(len(img_scales))])
+
+    def matches(self, device, B, V, H, W, img_scales, inter_scales, is_test, num_depth):
+        return (self.H, self.W) == (H, W) and self._same(device, B, V, num_depth, img_scales, inter_scales, is_test)
+
+
+class TrainPlan(_PlanBlock):
+    """The constants of the AUTOGRAD route (reference model.py:45-305; also every forward with B > 1), so forward +
+    loss + backward can be captured in a hipGraph and replayed on the next scene (train_step.GraphedTrainStep)."""
 
     def __init__(self, device, B, V, num_depth, img_scales, inter_scales, is_test):
-        self.device, self.B, self.V, self.D = device, B, V, int(num_depth)
-        self.img_scales, self.inter_scales = tuple(img_scales), tuple(inter_scales)
-        self.is_test = bool(is_test)
         entries = [("K_coarse", (B, V, 3, 3)), ("ext", (B, V, 3, 4)), ("Kinv0", (B, 1, 3, 3)), ("Rinv0", (B, 1, 3, 3)),
-                   ("t0", (B, 1, 3, 1)), ("depths", (B, self.D)), ("d_start", (B,)), ("d_int", (B,)),
+                   ("t0", (B, 1, 3, 1)), ("depths", (B, int(num_depth))), ("d_start", (B,)), ("d_int", (B,)),
                    ("mean", (B, 3, 1)), ("std", (B, 3, 1)), ("sa_params", (B, 3))]
-        for i in range(len(self.img_scales)):
+        for i in range(len(img_scales)):
             entries += [("interval%d" % i, (B,)), ("K_flow%d" % i, (B, V, 3, 3)), ("Kinv_flow%d" % i, (B, 1, 3, 3)),
                         ("pack%d" % i, (B, 27 + 21 * V + 1))]      # the PF_CAM_* block + interval of the fused kernels
-        self._layout, off = {}, 0
-        for name, shape in entries:
-            n = 1
-            for d in shape:
-                n *= d
-            self._layout[name] = (off, n, shape)
-            off += (n + 3) // 4 * 4
-        self.host = torch.zeros(off, dtype=torch.float32)
-        if torch.cuda.is_available():
-            self.host = self.host.pin_memory()
-        self.dev = torch.zeros(off, dtype=torch.float32, device=device)
-        self._copied = None
+        _PlanBlock.__init__(self, device, B, V, num_depth, img_scales, inter_scales, is_test, entries)
 
-    def _h(self, name):
-        off, n, shape = self._layout[name]
-        return self.host[off:off + n].view(shape)
-
-    def d(self, name):
-        off, n, shape = self._layout[name]
-        return self.dev[off:off + n].view(shape)
-
-    def matches(self, device, B, V, num_depth, img_scales, inter_scales, is_test):
-        return (self.device == device and (self.B, self.V, self.D) == (B, V, int(num_depth))
-                and self.img_scales == tuple(img_scales) and self.inter_scales == tuple(inter_scales)
-                and self.is_test == bool(is_test))
-
-    def fill_host_(self, data_batch):
-        cam = _Cameras(_host_cams(data_batch), self.is_test)
-        if cam.num_depth != self.D:
-            raise RuntimeError("TrainPlan: num_depth changed (%d -> %d); build a new plan" % (self.D, cam.num_depth))
-        mean_h = data_batch["mean_host"] if "mean_host" in data_batch else data_batch["mean"].detach().cpu()
-        std_h = data_batch["std_host"] if "std_host" in data_batch else data_batch["std"].detach().cpu()
-        if self._copied is not None:
-            self._copied.synchronize()
-        self._h("K_coarse").copy_(cam.K_coarse)
-        self._h("ext").copy_(cam.ext)
-        self._h("Kinv0").copy_(torch.inverse(cam.K_coarse[:, 0]).unsqueeze(1))
-        self._h("Rinv0").copy_(cam.R_inv[:, 0:1])
-        self._h("t0").copy_(cam.t[:, 0:1])
-        for b in range(self.B):
-            self._h("depths")[b].copy_(torch.linspace(float(cam.depth_start[b]), float(cam.depth_end[b]), self.D))
-        self._h("d_start").copy_(cam.depth_start)
-        self._h("d_int").copy_(cam.depth_interval)
-        self._h("sa_params").copy_(torch.stack([cam.depth_start, cam.depth_end, cam.depth_interval], dim=1))
-        self._h("mean").copy_(mean_h.float().reshape(self.B, 3, 1))
-        self._h("std").copy_(std_h.float().reshape(self.B, 3, 1))
-        for i, (s, inter) in enumerate(zip(self.img_scales, self.inter_scales)):
-            K_flow = cam.flow_intrinsics(s)
-            self._h("interval%d" % i).copy_(inter * cam.depth_interval)
-            self._h("K_flow%d" % i).copy_(K_flow)
-            self._h("Kinv_flow%d" % i).copy_(torch.inverse(K_flow[:, 0]).unsqueeze(1))
-            self._h("pack%d" % i).copy_(cam.packed(K_flow, mean_h.float().reshape(self.B, 3),
-                                                   std_h.float().reshape(self.B, 3), inter * cam.depth_interval))
-        return self
-
-    def upload_(self):
-        self.dev.copy_(self.host, non_blocking=True)
-        if self.dev.is_cuda:
-            self._copied = torch.cuda.Event()
-            self._copied.record()
-        return self
-
-    def update_(self, data_batch):
-        return self.fill_host_(data_batch).upload_()
+    matches = _PlanBlock._same
 
 
 class PointMVSNet(nn.Module):
@@ -375,10 +335,24 @@ class PointMVSNet(nn.Module):
     # ------------------------------------------------------------------------------------------
     def make_plan(self, data_batch, img_scales, inter_scales, isTest):
         """Allocate the constant blocks for this shape of problem and fill them from ``data_batch``."""
+        return self._updated_plan("_plan", data_batch, img_scales, inter_scales, isTest, cached=False)
+
+    def _updated_plan(self, attr, data_batch, img_scales, inter_scales, isTest, cached=True):
+        """The plan of this shape of problem, filled from ``data_batch`` and uploaded: a ScenePlan for ``attr``
+        "_plan", a TrainPlan for "_tplan".  ``cached`` reuses the module's plan under that attribute while it still
+        matches (and keeps a newly built one there); otherwise the caller owns a fresh plan."""
         img_list = data_batch["img_list"]
         B, V, _, H, W = img_list.shape
         D = int(_host_cams(data_batch)[0, 0, 1, 3, 2].long())
-        plan = ScenePlan(img_list.device, B, V, H, W, img_scales, inter_scales, isTest, D)
+        if attr == "_plan":
+            cls, key = ScenePlan, (img_list.device, B, V, H, W, img_scales, inter_scales, isTest, D)
+        else:
+            cls, key = TrainPlan, (img_list.device, B, V, D, img_scales, inter_scales, isTest)
+        plan = getattr(self, attr) if cached else None
+        if plan is None or not plan.matches(*key):
+            plan = cls(*key)
+            if cached:
+                setattr(self, attr, plan)
         return plan.update_(data_batch)
 
     def forward(self, data_batch, img_scales, inter_scales, isFlow, isTest=False):
@@ -386,19 +360,13 @@ class PointMVSNet(nn.Module):
         if not img_list.is_cuda:
             raise RuntimeError("pointmvsnet_amd.PointMVSNet runs on a GPU (HIP) device only; the CPU "
                                "restatement lives in oracle/ and is test infrastructure")
-        B, V, _, H, W = img_list.shape
-        if self._needs_graph() or B > 1:
+        if self._needs_graph() or img_list.shape[0] > 1:
             # The fused pipeline is built for one scene per call (the reference's test path asserts
             # TEST.BATCH_SIZE == 1, test.py:116).  With B > 1 every BatchNorm of the PointFlow stage pools its
             # statistics over the batch (networks.py:41,77; nn/conv.py:31-32); the composed path below does
             # exactly that, with or without autograd.
             return self._forward_autograd(data_batch, img_scales, inter_scales, isFlow, isTest)
-        D = int(_host_cams(data_batch)[0, 0, 1, 3, 2].long())
-        plan = self._plan
-        if plan is None or not plan.matches(img_list.device, B, V, H, W, img_scales, inter_scales, isTest, D):
-            plan = self._plan = ScenePlan(img_list.device, B, V, H, W, img_scales, inter_scales, isTest, D)
-        plan.update_(data_batch)
-        return self.run(plan, img_list, isFlow)
+        return self.run(self._updated_plan("_plan", data_batch, img_scales, inter_scales, isTest), img_list, isFlow)
 
     def run(self, plan, img_list, isFlow=True):
         """Device-only inference forward (capturable in a hipGraph): fused HIP pipeline, SURVEY.md section 8.
@@ -509,25 +477,15 @@ class PointMVSNet(nn.Module):
 
     # ------------------------------------------------------------------------------------------
     def make_train_plan(self, data_batch, img_scales, inter_scales, isTest=False):
-        img_list = data_batch["img_list"]
-        B, V = img_list.shape[:2]
-        D = int(_host_cams(data_batch)[0, 0, 1, 3, 2].long())
-        return TrainPlan(img_list.device, B, V, D, img_scales, inter_scales, isTest).update_(data_batch)
+        return self._updated_plan("_tplan", data_batch, img_scales, inter_scales, isTest, cached=False)
 
     def _forward_autograd(self, data_batch, img_scales, inter_scales, isFlow, isTest, tplan=None):
         """Training path: the reference composition on differentiable HIP operators (model.py:45-305).  Every
         host-derived constant comes from ``tplan`` (a TrainPlan; built and uploaded here when None), so with a
         caller-owned plan the whole pass is device-only and capturable."""
-        img_list = data_batch["img_list"]
-        dev = img_list.device
-        B, V, _, H, W = img_list.shape
         if tplan is None:
-            D = int(_host_cams(data_batch)[0, 0, 1, 3, 2].long())
-            tplan = self._tplan
-            if tplan is None or not tplan.matches(dev, B, V, D, img_scales, inter_scales, isTest):
-                tplan = self._tplan = TrainPlan(dev, B, V, D, img_scales, inter_scales, isTest)
-            tplan.update_(data_batch)
-        return self.run_autograd(tplan, img_list, isFlow)
+            tplan = self._updated_plan("_tplan", data_batch, img_scales, inter_scales, isTest)
+        return self.run_autograd(tplan, data_batch["img_list"], isFlow)
 
     def _coarse_cost_autograd(self, feature_list, world_points, K_coarse, ext, D):
         """The reference's coarse cost volume (model.py:102-111) composed from differentiable operators: (B, C, N)."""

@@ -273,6 +273,25 @@ def test_library_convolution_fallback_is_announced_once(dev):
     assert want["conv3"].shape == again["conv3"].shape == (1, 96, 8, 10)
 
 
+def test_plan_device_blocks_mirror_the_pinned_host_blocks_after_two_updates(dev):
+    """Both plans on the GPU: the pinned host block, the asynchronous copy and the wait that keeps the second host
+    fill from overtaking the first copy (no CPU test reaches them).  After two updates every device entry equals its
+    host entry -- the second scene's."""
+    from pointmvsnet_amd.model import ScenePlan, TrainPlan
+    data_a, img_scales, inter_scales = synthetic.make_config("tiny", seed=0)
+    data_b, _, _ = synthetic.make_config("tiny", seed=4)
+    for plan in (ScenePlan(dev, 1, 3, 128, 192, img_scales, inter_scales, True, 8),
+                 TrainPlan(dev, 1, 3, 8, img_scales, inter_scales, True)):
+        assert plan.host.is_pinned() or not torch.cuda.is_available()
+        plan.update_(_to(data_a, dev))
+        first = plan.host.clone()
+        plan.update_(_to(data_b, dev))
+        torch.cuda.synchronize()
+        assert not torch.equal(plan.host, first)
+        for name in plan._layout:
+            assert torch.equal(plan.d(name).cpu(), plan._h(name)), (type(plan).__name__, name)
+
+
 def test_graphed_forward_matches_eager_and_replays_on_new_scenes(dev):
     from pointmvsnet_amd.graph import GraphedForward
     data_a, img_scales, inter_scales = synthetic.make_config("tiny", seed=0)

@@ -73,8 +73,9 @@ def test_scene_plan_blocks_are_one_aligned_buffer():
     assert torch.equal(plan.d("depths")[0], torch.linspace(425.0, float(cam.depth_end[0]), 8))
     assert torch.equal(plan.d("sa_params")[0], torch.stack([cam.depth_start[0], cam.depth_end[0], cam.depth_interval[0]]))
     assert torch.equal(plan.d("pack1")[0, -1], (0.75 * cam.depth_interval)[0])
-    for name in ("K_coarse", "ext", "Kinv0", "Rinv0", "t0", "depths", "sa_params", "pack0", "pack1"):
-        assert plan.d(name).data_ptr() % 16 == 0
+    assert {"K_coarse", "ext", "Kinv0", "Rinv0", "t0", "depths", "sa_params", "pack0", "pack1"} <= set(plan._layout)
+    for name in plan._layout:
+        assert plan.d(name).data_ptr() % 16 == 0 and plan._h(name).data_ptr() % 16 == 0, name
     assert plan.matches(torch.device("cpu"), 1, 3, 128, 192, scales, inters, True, 8)
     assert not plan.matches(torch.device("cpu"), 1, 3, 128, 192, scales, inters, False, 8)
     other, _, _ = synthetic.make_config("tiny", seed=4)
@@ -100,8 +101,9 @@ def test_train_plan_holds_every_host_constant_of_the_autograd_forward():
         assert torch.equal(plan.d("K_flow%d" % i), K_flow)
         assert torch.equal(plan.d("Kinv_flow%d" % i)[:, 0], torch.inverse(K_flow[:, 0]))
         assert torch.equal(plan.d("interval%d" % i), inter * cam.depth_interval)
-        for name in ("K_flow%d" % i, "Kinv_flow%d" % i, "interval%d" % i):
-            assert plan.d(name).data_ptr() % 16 == 0
+        assert {"K_flow%d" % i, "Kinv_flow%d" % i, "interval%d" % i, "pack%d" % i} <= set(plan._layout)
+    for name in plan._layout:
+        assert plan.d(name).data_ptr() % 16 == 0 and plan._h(name).data_ptr() % 16 == 0, name
     assert plan.matches(torch.device("cpu"), 1, 3, 8, scales, inters, False)
     assert not plan.matches(torch.device("cpu"), 1, 3, 8, scales, inters, True)
     other, _, _ = synthetic.make_config("tiny", seed=4, train_intrinsics=True)
@@ -245,31 +247,61 @@ def test_deferred_batchnorm_jobs_are_layered_by_module_call_order(monkeypatch):
     assert launches == []
 
 
+def test_plans_refuse_a_batch_with_another_num_depth():
+    """The block's ``depths`` slice is sized by ``num_depth``: a batch with another one needs a new plan, and each
+    plan says so under its own name."""
+    from pointmvsnet_amd.model import ScenePlan, TrainPlan
+    data, scales, inters = synthetic.make_config("tiny")
+    other = synthetic.make_scene(128, 192, 3, 6)
+    cpu = torch.device("cpu")
+    for plan in (ScenePlan(cpu, 1, 3, 128, 192, scales, inters, True, 8), TrainPlan(cpu, 1, 3, 8, scales, inters, True)):
+        plan.update_(data)
+        kept = plan.host.clone()
+        with pytest.raises(RuntimeError, match=r"^%s: num_depth changed \(8 -> 6\)" % type(plan).__name__):
+            plan.update_(other)
+        assert torch.equal(plan.host, kept)                 # refused before the first write into the block
+
+
 @pytest.mark.parametrize("cfg,batch", [("cfg2", 1), ("cfg3", 1), ("cfg5", 1), ("tiny", 2)])
 @pytest.mark.parametrize("is_test", [True, False])
 def test_scene_plan_block_equals_the_reference_camera_algebra_bit_for_bit(cfg, batch, is_test):
-    """ScenePlan.fill_host_ (a dozen NumPy / LAPACK operations per scene) against the ``_Cameras`` composition, which
-    issues the reference's own ATen-CPU calls (reference model.py:54-61, :159-170): every float of the block equal."""
-    from pointmvsnet_amd.model import ScenePlan, _Cameras, _host_cams
+    """The plans' ``fill_host_`` (a dozen NumPy / LAPACK operations per scene) against the ``_Cameras`` composition,
+    which issues the reference's own ATen-CPU calls (reference model.py:54-61, :159-170): every float of every entry of
+    ScenePlan and of TrainPlan equal (TrainPlan on train-mode intrinsics when ``is_test`` is false)."""
+    from pointmvsnet_amd.model import ScenePlan, TrainPlan, _Cameras, _host_cams
+    cpu = torch.device("cpu")
     for seed in (0, 3):
-        if batch == 1:
-            data, scales, inters = synthetic.make_config(cfg, seed=seed)
-        else:
-            data, scales, inters = synthetic.make_scene(128, 192, 3, 8, seed=11 + seed, batch=batch), (0.125, 0.25), (1.0, 0.75)
-        B, V, _, H, W = data["img_list"].shape
-        D = int(data["cam_params_list"][0, 0, 1, 3, 2])
-        plan = ScenePlan(torch.device("cpu"), B, V, H, W, scales, inters, is_test, D).fill_host_(data)
-        cam = _Cameras(_host_cams(data), is_test)
-        want = {"K_coarse": cam.K_coarse, "ext": cam.ext, "Kinv0": torch.inverse(cam.K_coarse[:, 0]),
-                "Rinv0": cam.R_inv[:, 0], "t0": cam.t[:, 0],
-                "depths": torch.stack([torch.linspace(float(cam.depth_start[b]), float(cam.depth_end[b]), D)
-                                       for b in range(B)]),
-                "sa_params": torch.stack([cam.depth_start, cam.depth_end, cam.depth_interval], dim=1)}
-        for i, (s, inter) in enumerate(zip(scales, inters)):
-            want["pack%d" % i] = cam.packed(cam.flow_intrinsics(s), data["mean"], data["std"], inter * cam.depth_interval)
-        for name, t in want.items():
-            got = plan._h(name)
-            assert torch.equal(got, t.reshape(got.shape).float()), (cfg, seed, is_test, name)
+        for kind in (ScenePlan, TrainPlan):
+            train = kind is TrainPlan and not is_test
+            if batch == 1:
+                data, scales, inters = synthetic.make_config(cfg, seed=seed, train_intrinsics=train)
+            else:
+                data = synthetic.make_scene(128, 192, 3, 8, seed=11 + seed, batch=batch, train_intrinsics=train)
+                scales, inters = (0.125, 0.25), (1.0, 0.75)
+            B, V, _, H, W = data["img_list"].shape
+            D = int(data["cam_params_list"][0, 0, 1, 3, 2])
+            if kind is ScenePlan:
+                plan = ScenePlan(cpu, B, V, H, W, scales, inters, is_test, D).fill_host_(data)
+            else:
+                plan = TrainPlan(cpu, B, V, D, scales, inters, is_test).fill_host_(data)
+            cam = _Cameras(_host_cams(data), is_test)
+            want = {"K_coarse": cam.K_coarse, "ext": cam.ext, "Kinv0": torch.inverse(cam.K_coarse[:, 0]),
+                    "Rinv0": cam.R_inv[:, 0], "t0": cam.t[:, 0],
+                    "depths": torch.stack([torch.linspace(float(cam.depth_start[b]), float(cam.depth_end[b]), D)
+                                           for b in range(B)]),
+                    "sa_params": torch.stack([cam.depth_start, cam.depth_end, cam.depth_interval], dim=1),
+                    "d_start": cam.depth_start, "d_int": cam.depth_interval, "mean": data["mean"], "std": data["std"]}
+            for i, (s, inter) in enumerate(zip(scales, inters)):
+                K_flow = cam.flow_intrinsics(s)
+                want["interval%d" % i] = inter * cam.depth_interval
+                want["K_flow%d" % i] = K_flow
+                want["Kinv_flow%d" % i] = torch.inverse(K_flow[:, 0])
+                want["pack%d" % i] = cam.packed(K_flow, data["mean"], data["std"], inter * cam.depth_interval)
+            assert set(plan._layout) <= set(want)
+            assert kind is ScenePlan or set(plan._layout) == set(want)      # TrainPlan declares every one of them
+            for name in plan._layout:
+                got = plan._h(name)
+                assert torch.equal(got, want[name].reshape(got.shape).float()), (kind.__name__, cfg, seed, is_test, name)
 
 
 def test_flat_rmsprop_state_is_interchangeable_with_torch_rmsprop():
