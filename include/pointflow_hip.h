@@ -595,6 +595,28 @@ int pf_cloud_obs_mask_f32(const float* points, int64_t n, const unsigned char* m
 int pf_cloud_above_plane_f32(const float* points, int64_t n, float a, float b, float c, float d, unsigned char* above,
                              void* stream);
 
+/* ---- rendering a point cloud into depth maps: a z-buffer point splat (csrc/cloud_render.hip) -----------------------
+ * The inverse of the fusers' back-projection, which the reference does not have (it scores depth maps against ground-truth
+ * depth maps; DTU's test scans ship a ground-truth cloud).  The specification is this project's own
+ * (pointmvsnet_amd/render.py).  Pixel centres at (x + 0.5, y + 0.5) as above.
+ *   proj (V, PF_RENDER_PROJ_FLOATS): K [R | t] (3x4 row-major), composed in float64 by the host and passed as float32
+ *   zbuf (V, h, w) 64-bit cells, set to all-ones by the caller on the same stream before the launch
+ * pf_cloud_splat_f32: per point n = (X, Y, Z) of points (N, 3) and view v, in float32 in this order:
+ *   qx = ((p0 X + p1 Y) + p2 Z) + p3, qy and z likewise from rows 1 and 2; skip unless depth_min < z < depth_max (false
+ *   for NaN); u = qx / z, v = qy / z; skip unless -splat <= u < w + splat and -splat <= v < h + splat (compared as floats);
+ *   (xc, yc) = floor(u, v); every pixel (x, y) of the map with |x - xc| <= splat and |y - yc| <= splat takes
+ *   zbuf[v][y][x] = min(zbuf[v][y][x], float_bits(z) << 32 | n) by a 64-bit unsigned atomic minimum: the nearest point
+ *   wins, among equal z the lowest index, whatever the order of arrival.  Non-finite coordinates are skipped by the tests.
+ *   0 <= splat <= PF_RENDER_MAX_SPLAT, N <= PF_RENDER_MAX_POINTS, maps within the limits of pf_fuse_stage_a_f32.
+ * pf_cloud_zbuf_decode: depth (V,h,w) = the float in a cell's upper half, 0 where the cell is all-ones; index (V,h,w) int32 =
+ *   its lower half, -1 where empty (an index past 2^31 - 1 appears as its bit pattern); index may be NULL: not written. */
+#define PF_RENDER_PROJ_FLOATS 12
+#define PF_RENDER_MAX_SPLAT 8
+#define PF_RENDER_MAX_POINTS 4294967294LL
+int pf_cloud_splat_f32(const float* points, int64_t N, const float* proj, int V, int h, int w, int splat, float depth_min,
+                       float depth_max, uint64_t* zbuf, void* stream);
+int pf_cloud_zbuf_decode(const uint64_t* zbuf, int V, int h, int w, float* depth, int* index, void* stream);
+
 /* ---- image preprocessing from decoded uint8 views (csrc/preprocess.hip) -----------------------------------------
  * What reference dataset.py:269-287 does on the host before it uploads float32: cv2.resize, crop_dtu_input and
  * norm_image (utils/preprocess.py:6-11,56-85).  Specification: pointmvsnet_amd/utils/preprocess.py (the resize is this

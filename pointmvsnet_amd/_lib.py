@@ -118,6 +118,8 @@ PROTOTYPES = {
     "pf_cloud_nn_wave_f32": ([_vp, _vp, _i64, _i64, _vp, _vp, _i64, _f, _f, _f, _f, _i, _i, _i, _f, _vp, _vp, _vp], _i),
     "pf_cloud_obs_mask_f32": ([_vp, _i64, _vp, _i, _i, _i, _f, _f, _f, _f, _vp, _vp], _i),
     "pf_cloud_above_plane_f32": ([_vp, _i64, _f, _f, _f, _f, _vp, _vp], _i),
+    "pf_cloud_splat_f32": ([_vp, _i64, _vp, _i, _i, _i, _i, _f, _f, _vp, _vp], _i),
+    "pf_cloud_zbuf_decode": ([_vp, _i, _i, _i, _vp, _vp, _vp], _i),
     "pf_preprocess_resize_u8": ([_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp], _i),
     "pf_preprocess_standardise_f32": ([_vp, _vp, _i, _i, _i, _vp, _vp], _i),
     "pf_scan_filter_supported": ([_i] * 7, _i),

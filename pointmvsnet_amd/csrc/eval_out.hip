@@ -89,14 +89,15 @@ int pf_eval_prob_filter_f32(const float* depth, const float* flow_conf, const fl
 
 // A build that is not hipcc's (no __HIP__: the host re-compilation of tests/hipemu, whose list of sources is fixed) gets
 // the next stage of the evaluation output, the fusion kernels, the scene input (preprocess.hip), the point-cloud
-// evaluation (cloud_eval.hip), the scan's confidence filter (scan_filter.hip) and the round-trip consistency filter
-// (geo_filter.hip) with this unit, so that such a library exports the whole C ABI.  hipcc compiles fusion.hip,
-// preprocess.hip, cloud_eval.hip, scan_filter.hip and geo_filter.hip as units of their own (build.SOURCES) and never takes
-// this branch.
+// evaluation (cloud_eval.hip), the scan's confidence filter (scan_filter.hip), the round-trip consistency filter
+// (geo_filter.hip) and the point-cloud renderer (cloud_render.hip) with this unit, so that such a library exports the whole
+// C ABI.  hipcc compiles fusion.hip, preprocess.hip, cloud_eval.hip, scan_filter.hip, geo_filter.hip and cloud_render.hip
+// as units of their own (build.SOURCES) and never takes this branch.
 #if !defined(__HIP__)
 #include "fusion.hip"
 #include "preprocess.hip"
 #include "cloud_eval.hip"
 #include "scan_filter.hip"
 #include "geo_filter.hip"
+#include "cloud_render.hip"
 #endif

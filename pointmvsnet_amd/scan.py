@@ -43,6 +43,7 @@ import torch
 from . import _lib
 from .fusion import fuse_depth_maps
 from .geometric import geometric_filter
+from .render import depth_map_errors, render_depth_maps
 from .utils.eval_file_logger import _resize_nearest, _scene_paths
 from .utils.io import write_ply
 
@@ -281,6 +282,16 @@ class ScanAccumulator(object):
         K, E = self.cameras()
         return fuse_depth_maps(self.filtered(), K, E, images=self.images(), disp_threshold=disp_threshold,
                                num_consistent=num_consistent, depth_min=depth_min, depth_max=depth_max)
+
+    def depth_errors(self, gt_points, thresholds, splat=1, filtered=True):
+        """``render.depth_map_errors`` of the accumulated depth maps -- ``filtered()``, or the raw ``predictions()[0]`` with
+        ``filtered=False`` -- against ``gt_points`` (N, 3) float32 on the GPU (the scan's ground-truth cloud) rendered into
+        ``cameras()`` at the depth maps' size with ``render.render_depth_maps(..., splat=splat)``."""
+        self._require_complete("depth_errors")
+        K, E = self.cameras()
+        pred = self.filtered() if filtered else self._depth
+        return depth_map_errors(pred, render_depth_maps(gt_points, K, E, int(pred.shape[1]), int(pred.shape[2]), splat=splat),
+                                thresholds)
 
     def write_ply(self, path, **fuse_kwargs):
         """Fuse (``fuse_kwargs``: those of ``fuse``, ``method`` among them) and write the cloud to ``path``; returns

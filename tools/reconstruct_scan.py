@@ -4,14 +4,17 @@ preprocessing, the network, the batched confidence filter, the fusion and, optio
     python tools/reconstruct_scan.py --root DTU --scan 9 --weights model.pth --out scan9.ply \
         [--mode LANCZOS4] [--init-prob-threshold 0.2] [--flow-prob-threshold 0.1] [--name flow2] \
         [--fusion roundtrip --num-src 10 --save-depth DIR] \
-        [--gt stl009_total.ply --obs-mask ObsMask9_10.mat --plane Plane9.mat]
+        [--gt stl009_total.ply --obs-mask ObsMask9_10.mat --plane Plane9.mat [--depth-errors --splat 1]]
 
 ``--weights`` is a ``torch.load``-able file: its ``"model"`` entry if it has one, a leading ``module.`` stripped from the
 keys.  ``--fusion roundtrip`` replaces the disparity fusion by the round-trip consistency filter
 (pointmvsnet_amd/geometric.py) against the first ``--num-src`` views that ``Cameras/pair.txt`` lists for every view (0: all
 other views); ``--save-depth DIR`` writes that filter's averaged depth map and mask of every view as ``%08d_geo.pfm`` and
 ``%08d_geo_mask.pfm``.  Prints one JSON line: the number of points, the kept share per view and, with ``--gt``, the dict of
-``evaluate_point_cloud``.
+``evaluate_point_cloud``.  With ``--gt --depth-errors`` a second JSON line follows: the ground-truth cloud rendered into every
+view (pointmvsnet_amd/render.py, ``--splat`` pixels around each projection) and ``depth_map_errors`` of the raw and of the
+filtered depth maps against it, per view and in total, at thresholds of 1 and 3 times the reference view's depth interval
+scaled for ``--name`` as ``PointMVSNetMetric`` scales it (coarse 1, flow1 0.75, flow2 0.375).
 """
 import argparse
 import json
@@ -45,6 +48,9 @@ def batches_of(dataset, dev):
         yield batch
 
 
+INTERVAL_SCALE = {"coarse_depth_map": 1.0, "flow1": 0.75, "flow2": 0.375}      # PointMVSNetMetric's, per stage
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--root", required=True, help="the DTU folder (Cameras/, Eval/Rectified/scan<N>/)")
@@ -73,6 +79,8 @@ def main():
     ap.add_argument("--gt", default=None, help="the scan's ground-truth cloud (PLY): score the result")
     ap.add_argument("--obs-mask", default=None, help="DTU's ObsMask<scan>_10.mat")
     ap.add_argument("--plane", default=None, help="DTU's Plane<scan>.mat")
+    ap.add_argument("--depth-errors", action="store_true", help="with --gt: one more JSON line of per-view depth errors")
+    ap.add_argument("--splat", type=int, default=1, help="--depth-errors: pixels around a projection that a point fills")
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args()
     import torch
@@ -120,8 +128,15 @@ def main():
             kw.update(obs_mask=torch.from_numpy(mask), bb_min=bb_min, res=res)
         if args.plane:
             kw.update(plane=io.load_dtu_plane(args.plane))
-        out["score"] = evaluation.evaluate_point_cloud(points, torch.from_numpy(io.load_ply_points(args.gt)).to(dev), **kw)
+        gt = torch.from_numpy(io.load_ply_points(args.gt)).to(dev)
+        out["score"] = evaluation.evaluate_point_cloud(points, gt, **kw)
     print(json.dumps(out))
+    if args.gt and args.depth_errors:
+        interval = float(dataset[0]["cam_params_list"][0, 1, 3, 1]) * INTERVAL_SCALE.get(args.name, 1.0)
+        thresholds = [interval, 3.0 * interval]
+        print(json.dumps({"scan": args.scan, "name": args.name, "splat": args.splat, "depth_interval": interval,
+                          "depth_errors_raw": acc.depth_errors(gt, thresholds, splat=args.splat, filtered=False),
+                          "depth_errors_filtered": acc.depth_errors(gt, thresholds, splat=args.splat, filtered=True)}))
 
 
 if __name__ == "__main__":
