@@ -554,6 +554,25 @@ int pf_geo_filter_f32(const float* depth, const float* view_maps, const int* sou
                       int h, int w, float pix_threshold, float rel_depth_threshold, int num_consistent, float depth_min,
                       float depth_max, int* count, float* depth_avg, float* point, unsigned char* emit, void* stream);
 
+/* ---- normal maps of depth maps; normals of the fused points (csrc/depth_normals.hip) ------------------------------
+ * What fusibile's clouds carry and the fusers above did not.  The specification is this project's own
+ * (pointmvsnet_amd/normals.py).  Maps, pixel centres and view_maps as above; only A is read.
+ * pf_depth_normals_f32: per pixel p = (x, y) of view i, in float32 in this order, with P(q) = (A_i (xq+.5, yq+.5, 1)) d_i(q)
+ *   (the camera centre is not added), valid(q) = q inside the map and depth_min < d(q) < depth_max, linked(q) = valid(q) and
+ *   |d(q) - d(p)| <= rel_jump * d(p):
+ *   tangent along e = (step, 0): P(p+e) - P(p-e) if both are linked, else P(p+e) - P(p), else P(p) - P(p-e), else none;
+ *   likewise along (0, step).  c = cross(tx, ty), n = c / |c|, negated if dot(n, P(p)) > 0 (it faces the camera).
+ *   normal (V,h,w,3) = n, or (0, 0, 0) if p is not valid, a tangent is missing, |c| is 0 or not finite, or the dot
+ *   product is exactly 0.  step >= 1.
+ * pf_fuse_normals_f32: for every pixel p of view i with emit[i][p] set (pf_fuse_mark), out[i][p] = s / |s| with
+ *   s = normal_maps[i][p] + the sum of normal_maps[j][match] over the slots of pf_fuse_stage_a_f32's match in ascending
+ *   order with match >= 0 (slot = j, or j - 1 behind i), or (0, 0, 0) if |s| is 0 or not finite.  Other rows of out
+ *   (V,h,w,3) are not written; pf_fuse_compact_f32 orders the rows like the points. */
+int pf_depth_normals_f32(const float* depth, const float* view_maps, int V, int h, int w, int step, float rel_jump,
+                         float depth_min, float depth_max, float* normal, void* stream);
+int pf_fuse_normals_f32(const float* normal_maps, const int* match, const unsigned char* emit, int V, int h, int w,
+                        float* out, void* stream);
+
 /* ---- point-cloud evaluation: thinning and nearest distances between unordered clouds (csrc/cloud_eval.hip) -------
  * DTU's accuracy / completeness step, which the reference does not have (a separate MATLAB program).  The specification
  * is this project's own (pointmvsnet_amd/evaluation.py).  A cloud is searched through a sparse grid

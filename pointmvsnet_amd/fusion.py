@@ -10,7 +10,8 @@ fusibile is neither claimed nor tested.  Known departures from what is known of 
   ``eval_file_logger.depth_to_points``, so an unfused point equals the matching row of the ``.xyz`` file the logger
   writes -- where fusibile uses integer centres;
 * the partner pixel is the one that CONTAINS the projection (floor), its depth is not interpolated;
-* no normal test (the reference disables it with ``normal_thresh=360``);
+* no normal test (the reference disables it with ``normal_thresh=360``); the normals that ``with_normals=True`` adds to
+  the cloud are those of ``normals.py``, estimated from the depth maps and never compared between views;
 * the output order is fixed: view-major, then row-major.  Two runs give identical bytes.
 
 Stage A, per reference view ``i`` and pixel ``p = (x, y)`` with ``depth_min < d_i(p) < depth_max``:
@@ -35,7 +36,7 @@ import os.path as osp
 import numpy as np
 import torch
 
-from . import _lib, camera_maps as cm
+from . import _lib, camera_maps as cm, normals as nm
 from .camera_maps import PAIR_FLOATS, VIEW_FLOATS  # noqa: F401
 from .utils.io import load_cam_dtu, load_pfm, write_ply
 
@@ -54,7 +55,7 @@ def _maps_of(cams):
 
 
 def fuse_depth_maps(depths, intrinsics, extrinsics, images=None, disp_threshold=0.12, num_consistent=3, depth_min=1e-3,
-                    depth_max=1e5, return_stages=False):
+                    depth_max=1e5, return_stages=False, with_normals=False, normal_step=1, normal_rel_jump=0.01):
     """Fuse ``depths`` (V, h, w) float32 on the GPU (0 = no depth; a sequence of (h, w) maps is stacked, maps of different
     sizes are an error, as in fusibile) with cameras ``intrinsics`` (V, 3, 3, of that h x w grid) and ``extrinsics``
     (V, 3, 4) or (V, 4, 4), optionally ``images`` (V, h, w, 3) uint8, by the specification in this module's docstring.
@@ -62,7 +63,11 @@ def fuse_depth_maps(depths, intrinsics, extrinsics, images=None, disp_threshold=
     Returns ``(points (N, 3) float32, colours (N, 3) uint8 or None)`` on the device of ``depths``; with
     ``return_stages`` a third value, the dict of the Stage A tensors ``count`` (V, h, w) int32, ``point`` (V, h, w, 3),
     ``colour`` (V, h, w, 3) or None, ``match`` (V, V-1, h, w) int32 and the Stage B mask ``emit`` (V, h, w) bool.
-    There is no CPU path."""
+    With ``with_normals`` the points' unit normals (N, 3) float32 follow ``colours`` (``(0, 0, 0)`` where undefined), from
+    ``normals.depth_normals(depths, ..., step=normal_step, rel_jump=normal_rel_jump)`` summed over a point's matches
+    (``normals.py``), and the stages gain those maps as ``normal`` (V, h, w, 3).  There is no CPU path."""
+    if with_normals:
+        normal_step, normal_rel_jump = nm.check_step("fuse_depth_maps", normal_step, normal_rel_jump)
     depths, images, V, h, w, dev = cm.normalise_inputs("fuse_depth_maps", depths, images, num_consistent)
     maps = _maps_of(cm.decompose("fuse_depth_maps", intrinsics, extrinsics, V))
     with _lib.on_device(dev):
@@ -82,9 +87,16 @@ def fuse_depth_maps(depths, intrinsics, extrinsics, images=None, disp_threshold=
             _lib.call("pf_fuse_mark", _lib.ptr(count), _lib.ptr(match), _lib.ptr(used), _lib.ptr(emit), V, i, h, w,
                       int(num_consistent), _lib.stream())
         points, colours = cm.compact(emit, point, colour)
+        if with_normals:
+            normal = nm.normal_maps(depths, view_maps, normal_step, normal_rel_jump, depth_min, depth_max)
+            normals = nm.fused_normals(normal, match, emit)
+    out = (points, colours) + ((normals,) if with_normals else ())
     if not return_stages:
-        return points, colours
-    return points, colours, {"count": count, "point": point, "colour": colour, "match": match, "emit": emit.bool()}
+        return out
+    stages = {"count": count, "point": point, "colour": colour, "match": match, "emit": emit.bool()}
+    if with_normals:
+        stages["normal"] = normal
+    return out + (stages,)
 
 
 def _load_image(path, h, w):

@@ -52,7 +52,7 @@ listed pairs are composed, so cost and memory are linear in the number of views.
 import numpy as np
 import torch
 
-from . import _lib, camera_maps as cm
+from . import _lib, camera_maps as cm, normals as nm
 
 _WHO = "geometric_filter"
 
@@ -118,7 +118,7 @@ def _source_table(sources, V):
 
 def geometric_filter(depths, intrinsics, extrinsics, images=None, sources=None, pix_threshold=1.0,
                      rel_depth_threshold=0.01, num_consistent=3, depth_min=1e-3, depth_max=1e5, return_points=True,
-                     return_stages=False):
+                     return_stages=False, with_normals=False, normal_step=1, normal_rel_jump=0.01):
     """Filter ``depths`` (V, h, w) float32 on the GPU (0 = no depth; a sequence of (h, w) maps is stacked) with cameras
     ``intrinsics`` (V, 3, 3, of that h x w grid) and ``extrinsics`` (V, 3, 4) or (V, 4, 4), optionally ``images``
     (V, h, w, 3) uint8, against the source views ``sources`` (V, M) (integers, ``-1`` pads; None: all other views) by the
@@ -126,9 +126,16 @@ def geometric_filter(depths, intrinsics, extrinsics, images=None, sources=None, 
 
     Returns ``(depth_avg (V, h, w) float32, mask (V, h, w) bool, count (V, h, w) int32)`` and, with ``return_points``,
     also ``(points (N, 3) float32, colours (N, 3) uint8 or None)``: five values; with ``return_stages`` last the dict of
-    the kernel's per-pixel ``point`` (V, h, w, 3) and ``emit`` (V, h, w) uint8.  Everything is on the device of ``depths``.
-    There is no CPU path."""
+    the kernel's per-pixel ``point`` (V, h, w, 3) and ``emit`` (V, h, w) uint8.  With ``with_normals`` (which needs
+    ``return_points``) the points' unit normals (N, 3) float32 follow ``colours``: the points are back-projections at
+    ``depth_avg``, so they are ``normals.depth_normals(depth_avg, ..., step=normal_step, rel_jump=normal_rel_jump)`` at the
+    masked pixels (``(0, 0, 0)`` where undefined), and the stages gain those maps as ``normal`` (V, h, w, 3).  No normal is
+    compared between views.  Everything is on the device of ``depths``.  There is no CPU path."""
     depths = cm.stack_depths(_WHO, depths, num_consistent)
+    if with_normals:
+        if not return_points:
+            raise ValueError("%s: with_normals needs return_points" % _WHO)
+        normal_step, normal_rel_jump = nm.check_step(_WHO, normal_step, normal_rel_jump)
     table = _source_table(sources, int(depths.shape[0]))               # a bad table is reported before a missing GPU
     depths, images, V, h, w, dev = cm.normalise_inputs(_WHO, depths, images, num_consistent)
     cams = cm.decompose(_WHO, intrinsics, extrinsics, V)
@@ -146,5 +153,10 @@ def geometric_filter(depths, intrinsics, extrinsics, images=None, sources=None, 
                   float(pix_threshold), float(rel_depth_threshold), int(num_consistent), float(depth_min), float(depth_max),
                   _lib.ptr(count), _lib.ptr(depth_avg), _lib.ptr(point), _lib.ptr(emit), _lib.stream(), algo_bytes=algo)
         out = (depth_avg, emit.bool(), count)
-        stages = ({"point": point, "emit": emit},) if return_stages else ()
-        return out + (cm.compact(emit, point, images) if return_points else ()) + stages
+        stages = {"point": point, "emit": emit}
+        if return_points:
+            out += cm.compact(emit, point, images)
+        if with_normals:
+            stages["normal"] = nm.normal_maps(depth_avg, view_maps, normal_step, normal_rel_jump, depth_min, depth_max)
+            out += (cm.compact(emit, stages["normal"], None)[0],)
+        return out + ((stages,) if return_stages else ())

@@ -43,6 +43,7 @@ import torch
 from . import _lib
 from .fusion import fuse_depth_maps
 from .geometric import geometric_filter
+from .normals import depth_normals
 from .render import depth_map_errors, render_depth_maps
 from .utils.eval_file_logger import _resize_nearest, _scene_paths
 from .utils.io import write_ply
@@ -161,7 +162,8 @@ def filter_depth_maps(depths, flow_probs, init_probs, init_prob_threshold=0.2, f
 class ScanAccumulator(object):
     """Collects the predictions of the ``view_num`` views of one scan on the device and turns them into the point cloud.
 
-    ``add(data_batch, preds)`` after every forward; then ``filtered()``, ``cameras()``, ``fuse()``, ``write_ply(path)``.
+    ``add(data_batch, preds)`` after every forward; then ``filtered()``, ``cameras()``, ``normals()``, ``fuse()``,
+    ``write_ply(path)``.
     ``name`` is the depth map that is fused (``preds[name]``, ``preds[name + "_prob"]``), ``mode`` and the thresholds are
     those of ``filter_depth_maps``; ``keep_images`` keeps the views' images for the cloud's colours."""
 
@@ -268,20 +270,33 @@ class ScanAccumulator(object):
         K, E = self.cameras()
         return geometric_filter(self.filtered(), K, E, images=self.images(), sources=sources, **kwargs)
 
-    def fuse(self, disp_threshold=0.12, num_consistent=3, depth_min=1e-3, depth_max=1e5, method="disparity", **kwargs):
+    def normals(self, step=1, rel_jump=0.01):
+        """``normals.depth_normals`` of ``filtered()`` and ``cameras()``: (V, h, w, 3) unit normals facing their camera."""
+        self._require_complete("normals")
+        K, E = self.cameras()
+        return depth_normals(self.filtered(), K, E, step=step, rel_jump=rel_jump)
+
+    def fuse(self, disp_threshold=0.12, num_consistent=3, depth_min=1e-3, depth_max=1e5, method="disparity",
+             with_normals=False, normal_step=1, normal_rel_jump=0.01, **kwargs):
         """``(points (N, 3) float32, colours (N, 3) uint8 or None)``: with ``method="disparity"`` through
         ``fuse_depth_maps``; with ``method="roundtrip"`` the cloud of ``geometric()`` (``disp_threshold`` is not used;
-        ``kwargs``: ``sources``, ``pix_threshold``, ``rel_depth_threshold``)."""
+        ``kwargs``: ``sources``, ``pix_threshold``, ``rel_depth_threshold``).  With ``with_normals`` a third value, the
+        points' normals (N, 3) float32 as the method's fuser defines them (``normals.py``)."""
         if method not in ("disparity", "roundtrip"):
             raise ValueError("ScanAccumulator.fuse: unknown method %r (disparity or roundtrip)" % (method,))
         self._require_complete("fuse")
+        normal_kwargs = {}
+        if with_normals:
+            normal_kwargs = {"with_normals": True, "normal_step": normal_step, "normal_rel_jump": normal_rel_jump}
         if method == "roundtrip":
-            return self.geometric(num_consistent=num_consistent, depth_min=depth_min, depth_max=depth_max, **kwargs)[3:5]
+            kwargs.update(normal_kwargs)
+            return self.geometric(num_consistent=num_consistent, depth_min=depth_min, depth_max=depth_max,
+                                  **kwargs)[3:6 if with_normals else 5]
         if kwargs:
             raise TypeError("ScanAccumulator.fuse: %s belong to method=\"roundtrip\"" % ", ".join(sorted(kwargs)))
         K, E = self.cameras()
         return fuse_depth_maps(self.filtered(), K, E, images=self.images(), disp_threshold=disp_threshold,
-                               num_consistent=num_consistent, depth_min=depth_min, depth_max=depth_max)
+                               num_consistent=num_consistent, depth_min=depth_min, depth_max=depth_max, **normal_kwargs)
 
     def depth_errors(self, gt_points, thresholds, splat=1, filtered=True):
         """``render.depth_map_errors`` of the accumulated depth maps -- ``filtered()``, or the raw ``predictions()[0]`` with
@@ -294,17 +309,19 @@ class ScanAccumulator(object):
                                 thresholds)
 
     def write_ply(self, path, **fuse_kwargs):
-        """Fuse (``fuse_kwargs``: those of ``fuse``, ``method`` among them) and write the cloud to ``path``; returns
-        ``(points, colours)``."""
-        points, colours = self.fuse(**fuse_kwargs)
-        write_ply(path, points.cpu().numpy(), None if colours is None else colours.cpu().numpy())
-        return points, colours
+        """Fuse (``fuse_kwargs``: those of ``fuse``, ``method`` and ``with_normals`` among them) and write the cloud to
+        ``path``; returns what ``fuse`` returned: ``(points, colours)`` and, ``with_normals``, the normals."""
+        fused = self.fuse(**fuse_kwargs)
+        write_ply(path, fused[0].cpu().numpy(), None if fused[1] is None else fused[1].cpu().numpy(),
+                  fused[2].cpu().numpy() if len(fused) > 2 else None)
+        return fused
 
 
 def reconstruct_scan(model, batches, img_scales=(0.125, 0.25, 0.5), inter_scales=(1.0, 0.75, 0.15), view_num=None,
                      fuse_kwargs=None, **accumulator_kwargs):
     """Run ``model`` on every ``data_batch`` of one scan (any iterable; one view as the reference each), accumulate the
-    views and fuse them: ``(points, colours, accumulator)``.
+    views and fuse them: ``(points, colours, accumulator)``, or ``(points, colours, normals, accumulator)`` when
+    ``fuse_kwargs`` asks ``with_normals``.
 
     A ``torch.nn.Module`` is called as the evaluation forward, ``model(data_batch, img_scales, inter_scales, isFlow=True,
     isTest=True)`` under ``torch.no_grad()``; anything else (a ``GraphedForward``) as ``model(data_batch)``.  ``view_num``
@@ -323,5 +340,4 @@ def reconstruct_scan(model, batches, img_scales=(0.125, 0.25, 0.5), inter_scales
             if index is None and "ref_img_path" not in data_batch:
                 index = position
             acc.add(data_batch, preds, view_index=index)
-    points, colours = acc.fuse(**(fuse_kwargs or {}))
-    return points, colours, acc
+    return tuple(acc.fuse(**(fuse_kwargs or {}))) + (acc,)

@@ -95,14 +95,21 @@ def write_cam_dtu(file, cam):
         f.write(cam_dtu_text(cam))
 
 
-def write_ply(file, points, colors=None):
-    """Binary little-endian PLY of a point cloud: ``x y z`` float32 per vertex, then ``red green blue`` uchar when
-    ``colors`` (N, 3) is given -- the vertex layout fusibile's final3d_model.ply carries, minus the normals."""
+def write_ply(file, points, colors=None, normals=None):
+    """Binary little-endian PLY of a point cloud: ``x y z`` float32 per vertex, then ``nx ny nz`` float32 when ``normals``
+    (N, 3) is given, then ``red green blue`` uchar when ``colors`` (N, 3) is given -- the vertex layout fusibile's
+    final3d_model.ply carries; without normals, that layout minus the normals."""
     points = np.ascontiguousarray(points, dtype="<f4")
     if points.ndim != 2 or points.shape[1] != 3:
         raise Exception("Points must have N x 3 dimensions.")
     fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
     header = "ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+    if normals is not None:
+        normals = np.ascontiguousarray(normals, dtype="<f4")
+        if normals.shape != points.shape:
+            raise Exception("Normals must have the shape of the points.")
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+        header += "property float nx\nproperty float ny\nproperty float nz\n"
     if colors is not None:
         colors = np.asarray(colors)
         if colors.shape != points.shape or colors.dtype != np.uint8:
@@ -112,6 +119,9 @@ def write_ply(file, points, colors=None):
     vertex = np.empty(points.shape[0], dtype=np.dtype(fields))
     for c, n in enumerate("xyz"):
         vertex[n] = points[:, c]
+    if normals is not None:
+        for c, n in enumerate(("nx", "ny", "nz")):
+            vertex[n] = normals[:, c]
     if colors is not None:
         for c, n in enumerate(("red", "green", "blue")):
             vertex[n] = colors[:, c]
@@ -120,8 +130,9 @@ def write_ply(file, points, colors=None):
         f.write(vertex.tobytes())
 
 
-def load_ply(file):
-    """(points (N, 3) float32, colors (N, 3) uint8 or None) of a PLY file as ``write_ply`` writes it."""
+def load_ply(file, return_normals=False):
+    """(points (N, 3) float32, colors (N, 3) uint8 or None) of a PLY file as ``write_ply`` writes it; with
+    ``return_normals`` a third value, the normals (N, 3) float32, or None if the file has none."""
     with open(file, "rb") as f:
         if f.readline().strip() != b"ply":
             raise Exception("Not a PLY file.")
@@ -142,16 +153,20 @@ def load_ply(file):
             if words[0] == "property":
                 props.append((words[1], words[2]))
         xyz = [("float", n) for n in "xyz"]
+        nrm = [("float", n) for n in ("nx", "ny", "nz")]
         rgb = [("uchar", n) for n in ("red", "green", "blue")]
-        if count is None or props not in (xyz, xyz + rgb):
-            raise Exception("Only x y z float [red green blue uchar] vertices are read.")
+        if count is None or props not in (xyz, xyz + rgb, xyz + nrm, xyz + nrm + rgb):
+            raise Exception("Only x y z float [nx ny nz float] [red green blue uchar] vertices are read.")
         dtype = np.dtype([(n, "<f4" if t == "float" else "u1") for t, n in props])
         vertex = np.frombuffer(f.read(count * dtype.itemsize), dtype=dtype, count=count)
+    names = [n for _, n in props]
     points = np.stack([vertex[n] for n in "xyz"], axis=1) if count else np.zeros((0, 3), np.float32)
-    if len(props) == 3:
-        return points, None
-    colors = np.stack([vertex[n] for n in ("red", "green", "blue")], axis=1) if count else np.zeros((0, 3), np.uint8)
-    return points, colors
+    colors = normals = None
+    if "red" in names:
+        colors = np.stack([vertex[n] for n in ("red", "green", "blue")], axis=1) if count else np.zeros((0, 3), np.uint8)
+    if "nx" in names:
+        normals = np.stack([vertex[n] for n in ("nx", "ny", "nz")], axis=1) if count else np.zeros((0, 3), np.float32)
+    return (points, colors, normals) if return_normals else (points, colors)
 
 
 _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "<i2", "int16": "<i2", "ushort": "<u2",

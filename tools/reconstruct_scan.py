@@ -3,16 +3,18 @@ preprocessing, the network, the batched confidence filter, the fusion and, optio
 
     python tools/reconstruct_scan.py --root DTU --scan 9 --weights model.pth --out scan9.ply \
         [--mode LANCZOS4] [--init-prob-threshold 0.2] [--flow-prob-threshold 0.1] [--name flow2] \
-        [--fusion roundtrip --num-src 10 --save-depth DIR] \
+        [--fusion roundtrip --num-src 10 --save-depth DIR] [--normals [--normal-step 2]] \
         [--gt stl009_total.ply --obs-mask ObsMask9_10.mat --plane Plane9.mat [--depth-errors --splat 1]]
 
 ``--weights`` is a ``torch.load``-able file: its ``"model"`` entry if it has one, a leading ``module.`` stripped from the
 keys.  ``--fusion roundtrip`` replaces the disparity fusion by the round-trip consistency filter
 (pointmvsnet_amd/geometric.py) against the first ``--num-src`` views that ``Cameras/pair.txt`` lists for every view (0: all
 other views); ``--save-depth DIR`` writes that filter's averaged depth map and mask of every view as ``%08d_geo.pfm`` and
-``%08d_geo_mask.pfm``.  Prints one JSON line: the number of points, the kept share per view and, with ``--gt``, the dict of
-``evaluate_point_cloud``.  With ``--gt --depth-errors`` a second JSON line follows: the ground-truth cloud rendered into every
-view (pointmvsnet_amd/render.py, ``--splat`` pixels around each projection) and ``depth_map_errors`` of the raw and of the
+``%08d_geo_mask.pfm``.  ``--normals`` writes the oriented cloud, ``x y z nx ny nz [red green blue]`` per vertex: normals from
+the depth maps (pointmvsnet_amd/normals.py) with finite differences ``--normal-step`` pixels wide.  Prints one JSON line: the
+number of points, with ``--normals`` the number of them whose normal is undefined, the kept share per view and, with ``--gt``,
+the dict of ``evaluate_point_cloud``.  With ``--gt --depth-errors`` a second JSON line follows: the ground-truth cloud rendered
+into every view (pointmvsnet_amd/render.py, ``--splat`` pixels around each projection) and ``depth_map_errors`` of the raw and of the
 filtered depth maps against it, per view and in total, at thresholds of 1 and 3 times the reference view's depth interval
 scaled for ``--name`` as ``PointMVSNetMetric`` scales it (coarse 1, flow1 0.75, flow2 0.375).
 """
@@ -67,6 +69,8 @@ def main():
     ap.add_argument("--pix-threshold", type=float, default=1.0)
     ap.add_argument("--rel-depth-threshold", type=float, default=0.01)
     ap.add_argument("--save-depth", default=None, help="folder for the round-trip filter's %%08d_geo.pfm / %%08d_geo_mask.pfm")
+    ap.add_argument("--normals", action="store_true", help="write nx ny nz per vertex (normals from the depth maps)")
+    ap.add_argument("--normal-step", type=int, default=1, help="--normals: the finite-difference baseline in pixels")
     ap.add_argument("--name", default="flow2")
     ap.add_argument("--num-view", type=int, default=5)
     ap.add_argument("--height", type=int, default=960)
@@ -104,14 +108,20 @@ def main():
     fuse_kwargs = {"disp_threshold": args.disp_threshold, "num_consistent": args.num_consistent}
     if args.fusion == "roundtrip":
         fuse_kwargs = dict(geo_kwargs, method="roundtrip")
-    points, colours, acc = scan.reconstruct_scan(
+    if args.normals:
+        fuse_kwargs.update(with_normals=True, normal_step=args.normal_step)
+    points, colours, *normals, acc = scan.reconstruct_scan(
         net, batches_of(dataset, dev), tuple(args.img_scales), tuple(args.inter_scales), view_num=len(dataset),
         fuse_kwargs=fuse_kwargs, name=args.name,
         mode=args.mode, init_prob_threshold=args.init_prob_threshold, flow_prob_threshold=args.flow_prob_threshold)
-    io.write_ply(args.out, points.cpu().numpy(), None if colours is None else colours.cpu().numpy())
+    normals = normals[0] if normals else None
+    io.write_ply(args.out, points.cpu().numpy(), None if colours is None else colours.cpu().numpy(),
+                 None if normals is None else normals.cpu().numpy())
     filtered, kept = acc.filtered(return_kept=True)
     out = {"scan": args.scan, "views": len(dataset), "mode": args.mode, "fusion": args.fusion, "points": int(points.shape[0]), "out": args.out,
            "kept_share_per_view": [k / float(filtered[0].numel()) for k in kept.cpu().tolist()]}
+    if normals is not None:
+        out["normals_undefined"] = int((normals == 0).all(dim=1).sum())
     if args.save_depth:
         import numpy as np
         os.makedirs(args.save_depth, exist_ok=True)
