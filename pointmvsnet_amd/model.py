@@ -55,7 +55,8 @@ def join_fork_streams():
     """The current stream waits for everything the fork streams have been given.  Callers of ``backward()`` on a fused
     training forward run it before they read gradients: autograd joins a side stream at the end of backward only
     where an AccumulateGrad node ran on it, and with ``train_ops.direct_grads()`` the nodes add into the bucket
-    themselves."""
+    themselves.  Inside that block it also deals the weight gradients that waited for the end of the backward to the
+    current stream and the fork stream (without it they go out on one stream when the block is left)."""
     streams = list(_FORK_STREAMS.values())
     train_ops.flush_late(side=streams[0] if streams else None)   # weight gradients that waited for the end of the backward
     for stream in streams:

@@ -27,6 +27,7 @@ import torch
 from . import _lib
 from . import pointflow
 
+import collections
 import contextlib
 import ctypes
 import os
@@ -56,38 +57,6 @@ def _packed(kind, tensor):
     return None if _PACKS is None else _PACKS.get(kind, tensor)
 
 
-# True (train_step.TrainStep sets it around forward + backward): a node adds its parameter gradients straight into the
-# parameters' ``.grad`` tensors -- the views of the flat all-reduce bucket (distributed.GradBucket), zeroed at the start
-# of the step -- from inside its own kernels (their accumulate flags) and hands autograd None for them, instead of
-# returning 115 tensors that autograd then adds with one element-wise launch each (160 launches, 0.56 ms per step).
-DIRECT_GRADS = False
-
-
-@contextlib.contextmanager
-def direct_grads(on=True):
-    global DIRECT_GRADS
-    saved, DIRECT_GRADS = DIRECT_GRADS, bool(on)
-    if on:                                  # (a step that died in its backward must not leave launches for the next one)
-        _MAIN["stream"] = torch.cuda.current_stream() if torch.cuda.is_available() else None
-        del _WGRAD_DEFERRED[:]
-        del _LATE["wgrad"][:]
-        del _LATE["reduce"][:]
-    try:
-        yield
-    finally:
-        DIRECT_GRADS = saved
-
-
-def _grad_target(p):
-    """``p.grad`` when a node may accumulate into it directly, else None."""
-    if not DIRECT_GRADS:
-        return None
-    g = p.grad
-    if g is None or g.dtype != _F32 or g.shape != p.shape or not g.is_contiguous() or g.requires_grad:
-        return None
-    return g
-
-
 # The training forward's second stream (model.TRAIN_FORK): set by the model while a fused training forward that forked
 # the flow tower is being built, read by the nodes whose backward has work that only the flow tower's backward consumes
 # (level 2: the pyramid-level gradients of _FlowFeaturesTrain).  None: everything on the node's own stream.
@@ -112,173 +81,185 @@ def _on_side(min_level):
 # or the flow tower's stream -- were measured to LOSE 2-5 % beside the flow-tower fork: profiles/r04c_train_streams.md;
 # the variants are in git history, not here.)
 
-# Weight gradients that are ADDED into the bucket (direct_grads) leave their split partials in the workspace and queue the
-# reduction; a node's backward reduces all of its layers' partials in one launch when it returns
-# (pf_wgrad_reduce_batch_f32: the same fixed order per layer, 45 launches of ~5 us in the chain become 7).
-# PF_WGRAD_BATCH=0: one reduce launch per layer.
-WGRAD_BATCH = int(os.environ.get("PF_WGRAD_BATCH", "1"))
-_REDUCE_PENDING = []
+class _WgradLayer(collections.namedtuple(
+        "_WgradLayer", "gr x sc sh Cg Cx taps swapped work nbytes into flops bytes "
+                       "rows_P ldg ldx x_rows_per_stat N go xi k3 stride p3 sps",
+        defaults=(None,) * 11)):
+    """One queued weight gradient, as pf_conv_wgrad_batch_f32 launches it and pf_wgrad_reduce_batch_f32 adds it into the
+    gradient slot ``into``.  gr, x, Cg, Cx are the LAUNCH's operands (a swapped layer has them exchanged: conv_wgrad), sc /
+    sh the affine rows of x or None; a layer on point-major rows has rows_P .. x_rows_per_stat, a convolution N .. sps
+    (go, xi, k3, p3: the gradient's and the input's grid, kernel and padding as three numbers each).  The launch leaves
+    partials (splits, Cg, taps, Cx) in ``work``."""
+    __slots__ = ()
+
+    @property
+    def elems(self):
+        return self.Cg * self.Cx * self.taps
+
+    @property
+    def splits(self):
+        return self.nbytes // (4 * self.elems)
 
 
-def _queue_reduce(work, into, elems, nbytes, rows, taps=1, swapped=False):
-    """``rows`` / ``taps``: the Cg and the tap count of the launch that wrote ``work`` (its partials are (splits, rows, taps,
-    columns)); ``swapped``: a swapped-operand launch (_conv_wgrad_swapped)."""
-    late = (WGRAD_DEFER and WGRAD_LATE >= 2 and _MAIN["stream"] is not None
-            and torch.cuda.current_stream(work.device) == _MAIN["stream"])
-    (_LATE["reduce"] if late else _REDUCE_PENDING).append((work, into, int(elems), int(nbytes // (4 * elems)), int(rows), int(taps), int(bool(swapped)),
-                            torch.cuda.current_stream(work.device)))
+# The late weight gradients go out on WGRAD_STREAMS streams (2: the caller's and the fork stream; 1: one stream),
+# dealt by their flops: each is a chip-filling grid of 85-240 us that drains for a good part of its run time, and nothing
+# orders one layer's weight gradient against another's -- on two streams the drain of one overlaps the next one's start
+# (cfg-4 step 5.60 -> 5.50 ms, same box, three alternations; 3 and 4 streams measured no better: DESIGN.md section 10).
+WGRAD_STREAMS = 2
 
 
-# Convolution weight gradients that are ADDED into the bucket are not even launched where they are computed: a node queues
-# them and issues them together when its backward returns (pf_conv_wgrad_batch_f32: layers that share a kernel instantiation
-# ride in ONE grid -- VolumeConv's 96-384-block layers of ~20 us each beside conv1_0's), then the one batched reduction.
-# PF_WGRAD_DEFER=0: every layer launched in place (round 5's order).
-WGRAD_DEFER = int(os.environ.get("PF_WGRAD_DEFER", "1"))
-# ... and the 1x1 layers of the PointFlow nodes (EdgeConv chain, MLP: point-major rows) wait even longer: until the END of the
-# backward (flush_late(), called by model.join_fork_streams()), where the 25 600-point iteration's six launches of 10-30 us
-# ride in the grids of the 102 400-point iteration's (6.21 -> 6.10 ms per step).  2 (default): the convolution layers of the
-# nodes that run on the step's main stream (coarse tower, VolumeConv) wait for the end too (6.10 -> 6.07 ms); the flow tower's,
-# on its own stream, are issued there when its node returns.  PF_WGRAD_LATE=0: everything flushed with its own node.
-WGRAD_LATE = int(os.environ.get("PF_WGRAD_LATE", "2"))
-_WGRAD_DEFERRED = []
-_LATE = {"wgrad": [], "reduce": []}
+class _WgradQueue(object):
+    """The weight gradients of a step that ADDS them into the gradient bucket (direct_grads).  Nothing inside the step
+    reads one, so a layer is not launched where it is computed: it is queued, and a queue's layers are issued together
+    (pf_conv_wgrad_batch_f32: layers that share a kernel instantiation ride in ONE grid -- VolumeConv's 96-384-block
+    layers of ~20 us each beside conv1_0's), then reduced in one launch (pf_wgrad_reduce_batch_f32: the same fixed order
+    per layer, 45 launches of ~5 us in the chain become 7).
+
+    ``node``: issued when the node's backward returns (_with_packs).  ``late``: issued at the END of the backward
+    (flush_late(), called by model.join_fork_streams()) -- the layers computed on the step's main stream: there the
+    25 600-point PointFlow iteration's six launches of 10-30 us ride in the grids of the 102 400-point iteration's
+    (6.21 -> 6.10 ms per step), and the coarse tower's and VolumeConv's wait too (6.10 -> 6.07 ms).  The flow tower's, on
+    its own stream, go out there when its node returns: the end-of-backward flush runs BEFORE the main stream has waited
+    for the fork streams."""
+
+    def __init__(self):
+        self.node, self.late = [], []
+        self.direct, self.main = False, None         # inside direct_grads(True); the stream it was entered on
+
+    def __len__(self):
+        return len(self.node) + len(self.late)
+
+    def reset(self):
+        self.node, self.late = [], []
+
+    def add(self, layer):
+        if not self.direct:
+            raise RuntimeError("a weight gradient can be added into a gradient slot only inside direct_grads()")
+        if not layer.into.is_contiguous():
+            raise RuntimeError("a weight gradient can be added only into a contiguous gradient slot")
+        late = self.main is not None and torch.cuda.current_stream(layer.work.device) == self.main
+        (self.late if late else self.node).append(layer)
+
+    def flush_node(self):
+        todo, self.node = self.node, []
+        if todo:
+            _wgrad_launch(todo)
+            _reduce_launch(todo)
+
+    def flush_late(self, side=None):
+        todo, self.late = self.late, []
+        if not todo:
+            return
+        if side is None or WGRAD_STREAMS < 2 or len(todo) < 2:
+            _wgrad_launch(todo)
+        else:
+            if WGRAD_STREAMS > 2:
+                raise RuntimeError("WGRAD_STREAMS: 1 or 2 streams, not %d" % WGRAD_STREAMS)
+            groups, load = ([], []), [0.0, 0.0]
+            for layer in sorted(todo, key=lambda l: -l.flops):
+                g = load.index(min(load))                    # greedy: the next largest to the lighter stream
+                groups[g].append(layer)
+                load[g] += layer.flops
+            mine, theirs = groups                            # (neither is empty: every layer has flops)
+            cur = torch.cuda.current_stream(side.device)
+            side.wait_stream(cur)
+            with torch.cuda.stream(side):
+                _wgrad_launch(theirs)
+                for layer in theirs:
+                    layer.work.record_stream(side)
+            _wgrad_launch(mine)
+            cur.wait_stream(side)
+        # (the reductions stay on ONE stream, in queue order: two PointFlow iterations add into the same parameters'
+        # gradients -- on two streams that is a race, and it was measured to buy nothing: 5.50 -> 5.49 ms)
+        _reduce_launch(todo)
 
 
-_MAIN = {"stream": None}
+wgrad_queue = _WgradQueue()
 
 
-def _defer_wgrad(gr, x, N, Cg, Cx, go, xi, k3, stride, p3, sc, sh, sps, work, nbytes, flops, algo_bytes):
-    late = WGRAD_LATE >= 2 and _MAIN["stream"] is not None and torch.cuda.current_stream(gr.device) == _MAIN["stream"]
-    (_LATE["wgrad"] if late else _WGRAD_DEFERRED).append(dict(gr=gr, x=x, N=int(N), Cg=int(Cg), Cx=int(Cx), go=tuple(int(v) for v in go),
-                                xi=tuple(int(v) for v in xi), k3=tuple(int(v) for v in k3), stride=int(stride),
-                                p3=tuple(int(v) for v in p3), sc=sc, sh=sh, sps=int(sps), work=work, nbytes=int(nbytes),
-                                flops=float(flops), bytes=float(algo_bytes), rows=None))
+def flush_late(side=None):
+    """The end of a backward (model.join_fork_streams()): the weight gradients that waited for it, dealt to the current
+    stream and ``side``, then their reduction."""
+    wgrad_queue.flush_late(side)
 
 
-def _wgrad_launch_items(todo):
+@contextlib.contextmanager
+def direct_grads(on=True):
+    """Inside (train_step.TrainStep: around forward + backward) a node adds its parameter gradients straight into the
+    parameters' ``.grad`` tensors -- the views of the flat all-reduce bucket (distributed.GradBucket), zeroed at the start
+    of the step -- from inside its own kernels (their accumulate flags; the weight gradients through the queue above) and
+    hands autograd None for them, instead of returning 115 tensors that autograd then adds with one element-wise launch
+    each (160 launches, 0.56 ms per step).  Every queued weight gradient has been issued on the current stream when the
+    block is left; model.join_fork_streams() inside it, after backward(), deals them to two streams first."""
+    q = wgrad_queue
+    if len(q):
+        raise RuntimeError("direct_grads: %d weight gradients of an earlier backward are still queued" % len(q))
+    saved = q.direct, q.main
+    q.direct, q.main = bool(on), (torch.cuda.current_stream() if on and torch.cuda.is_available() else None)
+    try:
+        yield
+    except BaseException:
+        q.reset()                           # (a step that died in its backward must not leave launches for the next one)
+        raise
+    else:
+        q.flush_node()
+        q.flush_late()
+    finally:
+        q.direct, q.main = saved
+
+
+def _grad_target(p):
+    """``p.grad`` when a node may accumulate into it directly, else None."""
+    if not wgrad_queue.direct:
+        return None
+    g = p.grad
+    if g is None or g.dtype != _F32 or g.shape != p.shape or not g.is_contiguous() or g.requires_grad:
+        return None
+    return g
+
+
+def _wgrad_launch(todo):
     items = (_lib.WgradItem * len(todo))()
-    for it, d in zip(items, todo):
-        it.gr, it.x = d["gr"].data_ptr(), d["x"].data_ptr()
-        it.Cg, it.Cx = d["Cg"], d["Cx"]
-        it.x_scale = None if d["sc"] is None else d["sc"].data_ptr()
-        it.x_shift = None if d["sh"] is None else d["sh"].data_ptr()
-        it.workspace, it.workspace_bytes = d["work"].data_ptr(), d["nbytes"]
-        if d["rows"] is not None:
-            it.rows_P, it.ldg, it.ldx, it.x_rows_per_stat = d["rows"]
+    for it, l in zip(items, todo):
+        it.gr, it.x, it.Cg, it.Cx = l.gr.data_ptr(), l.x.data_ptr(), l.Cg, l.Cx
+        it.x_scale = None if l.sc is None else l.sc.data_ptr()
+        it.x_shift = None if l.sh is None else l.sh.data_ptr()
+        it.workspace, it.workspace_bytes = l.work.data_ptr(), l.nbytes
+        if l.rows_P is not None:
+            it.rows_P, it.ldg, it.ldx, it.x_rows_per_stat = l.rows_P, l.ldg, l.ldx, l.x_rows_per_stat
             it.stride = 1
             continue
-        it.N = d["N"]
-        it.Do, it.Ho, it.Wo = d["go"]
-        it.Di, it.Hi, it.Wi = d["xi"]
-        it.KD, it.KH, it.KW = d["k3"]
-        it.stride = d["stride"]
-        it.pd, it.ph, it.pw = d["p3"]
-        it.x_samples_per_stat = d["sps"]
-    with torch.cuda.device(todo[0]["gr"].device):
+        it.N, it.stride, it.x_samples_per_stat = l.N, l.stride, l.sps
+        it.Do, it.Ho, it.Wo = l.go
+        it.Di, it.Hi, it.Wi = l.xi
+        it.KD, it.KH, it.KW = l.k3
+        it.pd, it.ph, it.pw = l.p3
+    with torch.cuda.device(todo[0].gr.device):
         for base in range(0, len(todo), 64):                      # (the entry point takes <= 64 items)
             n = min(64, len(todo) - base)
             chunk = (_lib.WgradItem * n).from_address(ctypes.addressof(items) + base * ctypes.sizeof(_lib.WgradItem))
             _lib.call("pf_conv_wgrad_batch_f32", chunk, n, _lib.stream(),
-                      algo_bytes=sum(d["bytes"] for d in todo[base:base + n]),
-                      flops=sum(d["flops"] for d in todo[base:base + n]))
+                      algo_bytes=sum(l.bytes for l in todo[base:base + n]),
+                      flops=sum(l.flops for l in todo[base:base + n]))
 
 
-def _wgrad_flush_deferred():
-    if not _WGRAD_DEFERRED:
-        return
-    todo = list(_WGRAD_DEFERRED)
-    del _WGRAD_DEFERRED[:]
-    _wgrad_launch_items(todo)
-
-
-# The late weight gradients go out on PF_WGRAD_STREAMS streams (default 2: the caller's and a fork stream; 1 = one stream),
-# dealt by their flops: each is a chip-filling grid of 85-240 us that drains for a good part of its run time, and nothing
-# orders one layer's weight gradient against another's -- on two streams the drain of one overlaps the next one's start
-# (cfg-4 step 5.60 -> 5.50 ms, same box, three alternations).
-WGRAD_STREAMS = int(os.environ.get("PF_WGRAD_STREAMS", "2"))
-_EXTRA_STREAMS = {}
-
-
-def _wgrad_streams(side, n):
-    """``n`` - 1 streams beside the current one: the fork stream first, then streams of this module's own."""
-    out = [side]
-    key = str(side.device)
-    pool = _EXTRA_STREAMS.setdefault(key, [])
-    while len(pool) < n - 2:
-        pool.append(torch.cuda.Stream(device=side.device))
-    return out + pool[:max(0, n - 2)]
-
-
-def flush_late(side=None):
-    """The end of a backward (model.join_fork_streams()): the weight gradients that waited for it, then their reduction."""
-    todo, reds = list(_LATE["wgrad"]), list(_LATE["reduce"])
-    del _LATE["wgrad"][:]
-    del _LATE["reduce"][:]
-    if todo and WGRAD_STREAMS >= 2 and side is not None and len(todo) >= 2:
-        streams = _wgrad_streams(side, WGRAD_STREAMS)
-        groups = [[] for _ in range(len(streams) + 1)]       # groups[0]: the current stream
-        load = [0.0] * len(groups)
-        for i in sorted(range(len(todo)), key=lambda i: -todo[i].get("flops", 0.0)):
-            g = load.index(min(load))                        # greedy: the next largest to the lightest stream
-            groups[g].append(todo[i])
-            load[g] += todo[i].get("flops", 0.0)
-        cur = torch.cuda.current_stream(side.device)
-        for st, grp in zip(streams, groups[1:]):
-            if not grp:
-                continue
-            st.wait_stream(cur)
-            with torch.cuda.stream(st):
-                _wgrad_launch_items(grp)
-                for d in grp:
-                    d["work"].record_stream(st)
-        if groups[0]:
-            _wgrad_launch_items(groups[0])
-        for st, grp in zip(streams, groups[1:]):
-            if grp:
-                cur.wait_stream(st)
-        # (the reductions stay on ONE stream, in queue order: two PointFlow iterations add into the same parameters'
-        # gradients -- on two streams that is a race, and it was measured to buy nothing: 5.50 -> 5.49 ms)
-    elif todo:
-        _wgrad_launch_items(todo)
-    if reds:
-        with torch.cuda.device(reds[0][0].device):
-            for base in range(0, len(reds), 16):
-                _reduce_launch(reds[base:base + 16])
-
-
-def _reduce_flush():
-    """One pf_wgrad_reduce_batch_f32 launch per stream the node's weight gradients were issued on (normally one: the
-    current stream; with model.TRAIN_FORK = 3 the PointFlow nodes' weight gradients and their reduction run on the side
-    stream, where nothing of the chain waits for them)."""
-    _wgrad_flush_deferred()
-    if not _REDUCE_PENDING:
-        return
-    everything = list(_REDUCE_PENDING)
-    del _REDUCE_PENDING[:]
-    streams = []
-    for p in everything:
-        if not any(p[7] == st for st in streams):
-            streams.append(p[7])
-    for st in streams:
-        with torch.cuda.stream(st):
-            _reduce_launch([p for p in everything if p[7] == st])
-
-
-def _reduce_launch(pending):
-    n = len(pending)
-    parts = (ctypes.c_void_p * n)(*[p[0].data_ptr() for p in pending])
-    dws = (ctypes.c_void_p * n)(*[p[1].data_ptr() for p in pending])
-    elems = (ctypes.c_int64 * n)(*[p[2] for p in pending])
-    splits = (ctypes.c_int * n)(*[p[3] for p in pending])
-    rows = (ctypes.c_int * n)(*[p[4] for p in pending])
-    taps = (ctypes.c_int * n)(*[p[5] for p in pending])
-    swapped = (ctypes.c_int * n)(*[p[6] for p in pending])
-    with torch.cuda.device(pending[0][0].device):
+def _reduce_launch(todo):
+    with torch.cuda.device(todo[0].work.device):
         cur = torch.cuda.current_stream()
-        for p in pending:                      # (a partial may have been written on the side stream)
-            p[0].record_stream(cur)
-        _lib.call("pf_wgrad_reduce_batch_f32", parts, dws, elems, splits, rows, taps, swapped, n, 1, _lib.stream(),
-                  algo_bytes=4.0 * sum(p[2] * p[3] for p in pending))
+        for base in range(0, len(todo), 16):           # (one call per launch: kRedBatch of csrc/conv_wgrad.hip)
+            pending = todo[base:base + 16]
+            n = len(pending)
+            parts = (ctypes.c_void_p * n)(*[l.work.data_ptr() for l in pending])
+            dws = (ctypes.c_void_p * n)(*[l.into.data_ptr() for l in pending])
+            elems = (ctypes.c_int64 * n)(*[l.elems for l in pending])
+            splits = (ctypes.c_int * n)(*[l.splits for l in pending])
+            rows = (ctypes.c_int * n)(*[l.Cg for l in pending])
+            taps = (ctypes.c_int * n)(*[l.taps for l in pending])
+            swapped = (ctypes.c_int * n)(*[int(l.swapped) for l in pending])
+            for l in pending:                          # (a partial may have been written on the side stream)
+                l.work.record_stream(cur)
+            _lib.call("pf_wgrad_reduce_batch_f32", parts, dws, elems, splits, rows, taps, swapped, n, 1, _lib.stream(),
+                      algo_bytes=4.0 * sum(l.elems * l.splits for l in pending))
 
 
 def _with_packs(backward):
@@ -288,7 +269,7 @@ def _with_packs(backward):
             try:
                 return backward(ctx, *grads)
             finally:
-                _reduce_flush()
+                wgrad_queue.flush_node()
     return wrapped
 
 
@@ -477,49 +458,6 @@ def rows_affine(y, rows, C, G, Ng, groups_per_stat, relu=True):
     return z
 
 
-def conv_wgrad(gr, x, kernel, stride, pad, x_affine=None, x_samples_per_stat=1, into=None):
-    """dw (Cg, Cx, *kernel) = sum gr[n, cg, o] * act(x)[n, cx, o * stride + k - pad] (pf_conv_wgrad_f32).
-    gr (N, Cg, *coarse grid), x (N, Cx, *fine grid), 2-D or 3-D; x_affine = (scale, shift) rows of x's pending
-    BatchNorm + ReLU or None."""
-    nd = gr.dim() - 2
-    N, Cg = gr.shape[:2]
-    Cx = x.shape[1]
-    if (WGRAD_SWAP and stride == 1 and x_affine is None and Cg <= 8 and Cg < Cx and gr.shape[2:] == x.shape[2:]
-            and all(2 * p + 1 == k for p, k in zip(pad, kernel))):
-        return _conv_wgrad_swapped(gr, x, kernel, pad, into)
-    go = (1,) * (3 - nd) + tuple(gr.shape[2:])
-    xi = (1,) * (3 - nd) + tuple(x.shape[2:])
-    k3 = (1,) * (3 - nd) + tuple(kernel)
-    p3 = (0,) * (3 - nd) + tuple(pad)
-    lib = _lib.load()
-    nbytes = int(lib.pf_conv_wgrad_workspace(N, Cg, Cx, go[0], go[1], go[2], xi[0], xi[1], xi[2], k3[0], k3[1], k3[2],
-                                             int(stride)))
-    if nbytes < 0:
-        raise RuntimeError("conv_wgrad: unsupported shape")
-    sc, sh = (None, None) if x_affine is None else x_affine
-    taps = k3[0] * k3[1] * k3[2]
-
-    def launch():
-        work = torch.empty((max(nbytes, 4) // 4,), dtype=_F32, device=gr.device)
-        dw = torch.empty((Cg, Cx) + tuple(kernel), dtype=_F32, device=gr.device) if into is None else into   # into: dw +=
-        batched = into is not None and WGRAD_BATCH and DIRECT_GRADS and into.is_contiguous()
-        if batched and WGRAD_DEFER:
-            _defer_wgrad(gr, x, N, Cg, Cx, go, xi, k3, stride, p3, sc, sh, x_samples_per_stat, work, nbytes,
-                         2.0 * N * go[0] * go[1] * go[2] * taps * Cg * Cx, 4.0 * (gr.numel() + x.numel()) + 4.0 * dw.numel())
-            _queue_reduce(work, into, Cg * Cx * taps, nbytes, Cg, taps)
-            return None
-        _lib.call("pf_conv_wgrad_f32", _lib.ptr(gr), _lib.ptr(x), None if batched else _lib.ptr(dw), N, Cg, Cx, go[0],
-                  go[1], go[2], xi[0], xi[1], xi[2], k3[0], k3[1], k3[2], int(stride), p3[0], p3[1], p3[2], _lib.ptr(sc),
-                  _lib.ptr(sh), int(x_samples_per_stat), _lib.ptr(work), nbytes, 0 if into is None else 1, _lib.stream(),
-                  algo_bytes=4.0 * (gr.numel() + x.numel()) + 4.0 * dw.numel(),
-                  flops=2.0 * N * go[0] * go[1] * go[2] * taps * Cg * Cx)
-        if batched:
-            _queue_reduce(work, into, Cg * Cx * taps, nbytes, Cg, taps)
-        return dw if into is None else None
-
-    return launch()
-
-
 # Stride-1 'same' layers with at most 8 output channels (VolumeConv's conv0_1 64 -> 8 and conv6_2 8 -> 1): the operands
 # change places (include/pointflow_hip.h, pf_wgrad_reduce_batch_f32's `swapped`) -- the MFMA rows are the INPUT channels
 # (64 of 64 rows used instead of 8 of 16) and the patch that is staged with its halo is the 8-channel gradient instead of
@@ -527,79 +465,62 @@ def conv_wgrad(gr, x, kernel, stride, pad, x_affine=None, x_samples_per_stat=1, 
 WGRAD_SWAP = int(os.environ.get("PF_WGRAD_SWAP", "1"))
 
 
-def _conv_wgrad_swapped(gr, x, kernel, pad, into):
-    """conv_wgrad(gr, x) as pf_conv_wgrad_f32(gr' = x, x' = gr): partials (Cx, Cg, taps) with reversed taps, put into
-    nn.ConvNd's order by the batched reduce (the step) or by a transpose + flip (a stand-alone call)."""
+def conv_wgrad(gr, x, kernel, stride, pad, x_affine=None, x_samples_per_stat=1, into=None):
+    """dw (Cg, Cx, *kernel) = sum gr[n, cg, o] * act(x)[n, cx, o * stride + k - pad] (pf_conv_wgrad_f32).
+    gr (N, Cg, *coarse grid), x (N, Cx, *fine grid), 2-D or 3-D; x_affine = (scale, shift) rows of x's pending
+    BatchNorm + ReLU or None.  ``into`` (inside direct_grads): the gradient slot dw is ADDED to, by the step's queue;
+    returns None then."""
     nd = gr.dim() - 2
     N, Cg = gr.shape[:2]
     Cx = x.shape[1]
-    sp = (1,) * (3 - nd) + tuple(gr.shape[2:])
+    swapped = bool(WGRAD_SWAP and stride == 1 and x_affine is None and Cg <= 8 and Cg < Cx and gr.shape[2:] == x.shape[2:]
+                   and all(2 * p + 1 == k for p, k in zip(pad, kernel)))
+    if swapped:         # the launch leaves partials (Cx, Cg, taps) with reversed taps: put into nn.ConvNd's order by the
+        gr, x, Cg, Cx = x, gr, Cx, Cg                 # batched reduce (the step) or by a transpose + flip (stand-alone)
+    go = (1,) * (3 - nd) + tuple(gr.shape[2:])
+    xi = (1,) * (3 - nd) + tuple(x.shape[2:])
     k3 = (1,) * (3 - nd) + tuple(kernel)
     p3 = (0,) * (3 - nd) + tuple(pad)
     taps = k3[0] * k3[1] * k3[2]
-    lib = _lib.load()
-    nbytes = int(lib.pf_conv_wgrad_workspace(N, Cx, Cg, sp[0], sp[1], sp[2], sp[0], sp[1], sp[2], k3[0], k3[1], k3[2], 1))
+    nbytes = int(_lib.load().pf_conv_wgrad_workspace(N, Cg, Cx, go[0], go[1], go[2], xi[0], xi[1], xi[2], k3[0], k3[1],
+                                                     k3[2], int(stride)))
     if nbytes < 0:
         raise RuntimeError("conv_wgrad: unsupported shape")
+    sc, sh = (None, None) if x_affine is None else x_affine
     work = torch.empty((max(nbytes, 4) // 4,), dtype=_F32, device=gr.device)
-    batched = into is not None and WGRAD_BATCH and DIRECT_GRADS and into.is_contiguous()
-    if batched and WGRAD_DEFER:
-        _defer_wgrad(x, gr, N, Cx, Cg, sp, sp, k3, 1, p3, None, None, 1, work, nbytes,
-                     2.0 * N * sp[0] * sp[1] * sp[2] * taps * Cg * Cx, 4.0 * (gr.numel() + x.numel()) + 4.0 * Cg * Cx * taps)
-        _queue_reduce(work, into, Cg * Cx * taps, nbytes, Cx, taps, swapped=True)
+    flops = 2.0 * N * go[0] * go[1] * go[2] * taps * Cg * Cx
+    algo_bytes = 4.0 * (gr.numel() + x.numel()) + 4.0 * Cg * Cx * taps
+    if into is not None:
+        wgrad_queue.add(_WgradLayer(gr, x, sc, sh, Cg, Cx, taps, swapped, work, nbytes, into, flops, algo_bytes,
+                                    N=N, go=go, xi=xi, k3=k3, stride=int(stride), p3=p3, sps=int(x_samples_per_stat)))
         return None
-    dwt = None if batched else torch.empty((Cx, Cg) + tuple(kernel), dtype=_F32, device=gr.device)
-    _lib.call("pf_conv_wgrad_f32", _lib.ptr(x), _lib.ptr(gr), _lib.ptr(dwt), N, Cx, Cg, sp[0], sp[1], sp[2], sp[0], sp[1],
-              sp[2], k3[0], k3[1], k3[2], 1, p3[0], p3[1], p3[2], None, None, 1, _lib.ptr(work), nbytes, 0, _lib.stream(),
-              algo_bytes=4.0 * (gr.numel() + x.numel()) + 4.0 * Cg * Cx * taps,
-              flops=2.0 * N * sp[0] * sp[1] * sp[2] * taps * Cg * Cx)
-    if batched:
-        _queue_reduce(work, into, Cg * Cx * taps, nbytes, Cx, taps, swapped=True)
-        return None
-    dw = dwt.transpose(0, 1).flip(*range(2, 2 + nd)).contiguous()
-    if into is None:
-        return dw
-    into.add_(dw)
-    return None
+    dw = torch.empty((Cg, Cx) + tuple(kernel), dtype=_F32, device=gr.device)
+    _lib.call("pf_conv_wgrad_f32", _lib.ptr(gr), _lib.ptr(x), _lib.ptr(dw), N, Cg, Cx, go[0], go[1], go[2], xi[0], xi[1],
+              xi[2], k3[0], k3[1], k3[2], int(stride), p3[0], p3[1], p3[2], _lib.ptr(sc), _lib.ptr(sh),
+              int(x_samples_per_stat), _lib.ptr(work), nbytes, 0, _lib.stream(), algo_bytes=algo_bytes, flops=flops)
+    return dw.transpose(0, 1).flip(*range(2, 2 + nd)).contiguous() if swapped else dw
 
 
-def rows_wgrad(gr, x, Cg, Cx, x_affine=None, x_rows_per_stat=None, into=None, side=None):
-    """dw (Cg, Cx) = sum_p gr[p, :Cg]^T act(x[p, :Cx]) on point-major row views (pf_rows_wgrad_f32).  ``side``: a stream to
-    issue the launch (and, later, its reduction) on when the result is ADDED into the gradient bucket -- nothing inside the
-    step reads it, so the chain does not have to wait for it (model.TRAIN_FORK = 3)."""
-    P = gr.shape[0]
-    lib = _lib.load()
-    nbytes = int(lib.pf_rows_wgrad_workspace(P, int(Cg), int(Cx)))
+def rows_wgrad(gr, x, Cg, Cx, x_affine=None, x_rows_per_stat=None, into=None):
+    """dw (Cg, Cx) = sum_p gr[p, :Cg]^T act(x[p, :Cx]) on point-major row views (pf_rows_wgrad_f32).  ``into``: as in
+    conv_wgrad."""
+    P, Cg, Cx = gr.shape[0], int(Cg), int(Cx)
+    nbytes = int(_lib.load().pf_rows_wgrad_workspace(P, Cg, Cx))
     if nbytes < 0:
         raise RuntimeError("rows_wgrad: unsupported shape")
     sc, sh = (None, None) if x_affine is None else x_affine
-
-    def launch():
-        work = torch.empty((max(nbytes, 4) // 4,), dtype=_F32, device=gr.device)
-        dw = torch.empty((Cg, Cx), dtype=_F32, device=gr.device) if into is None else into
-        batched = into is not None and WGRAD_BATCH and DIRECT_GRADS and into.is_contiguous()
-        if batched and WGRAD_DEFER and WGRAD_LATE and side is None:
-            _LATE["wgrad"].append(dict(gr=gr, x=x, Cg=int(Cg), Cx=int(Cx), sc=sc, sh=sh, work=work, nbytes=int(nbytes),
-                                       flops=2.0 * P * Cg * Cx, bytes=4.0 * P * (Cg + Cx) + 4.0 * Cg * Cx,
-                                       rows=(int(P), int(gr.stride(0)), int(x.stride(0)), int(x_rows_per_stat or P))))
-            _LATE["reduce"].append((work, into, int(Cg) * int(Cx), int(nbytes // (4 * int(Cg) * int(Cx))), int(Cg), 1, 0,
-                                    torch.cuda.current_stream(work.device)))
-            return None
-        _lib.call("pf_rows_wgrad_f32", _lib.ptr(gr), int(gr.stride(0)), _lib.ptr(x), int(x.stride(0)),
-                  None if batched else _lib.ptr(dw), P, int(Cg), int(Cx), _lib.ptr(sc), _lib.ptr(sh),
-                  int(x_rows_per_stat or P), _lib.ptr(work), nbytes, 0 if into is None else 1, _lib.stream(),
-                  algo_bytes=4.0 * P * (Cg + Cx) + 4.0 * Cg * Cx, flops=2.0 * P * Cg * Cx)
-        if batched:
-            _queue_reduce(work, into, int(Cg) * int(Cx), nbytes, int(Cg), 1)
-        return dw if into is None else None
-
-    if side is not None and into is not None and WGRAD_BATCH and DIRECT_GRADS and into.is_contiguous():
-        side.wait_stream(torch.cuda.current_stream(gr.device))
-        for t in (gr, x) + (() if x_affine is None else tuple(x_affine)):
-            t.record_stream(side)
-        with torch.cuda.stream(side):
-            return launch()
-    return launch()
+    ldg, ldx, per_stat = int(gr.stride(0)), int(x.stride(0)), int(x_rows_per_stat or P)
+    work = torch.empty((max(nbytes, 4) // 4,), dtype=_F32, device=gr.device)
+    flops = 2.0 * P * Cg * Cx
+    algo_bytes = 4.0 * P * (Cg + Cx) + 4.0 * Cg * Cx
+    if into is not None:
+        wgrad_queue.add(_WgradLayer(gr, x, sc, sh, Cg, Cx, 1, False, work, nbytes, into, flops, algo_bytes,
+                                    rows_P=P, ldg=ldg, ldx=ldx, x_rows_per_stat=per_stat))
+        return None
+    dw = torch.empty((Cg, Cx), dtype=_F32, device=gr.device)
+    _lib.call("pf_rows_wgrad_f32", _lib.ptr(gr), ldg, _lib.ptr(x), ldx, _lib.ptr(dw), P, Cg, Cx, _lib.ptr(sc), _lib.ptr(sh),
+              per_stat, _lib.ptr(work), nbytes, 0, _lib.stream(), algo_bytes=algo_bytes, flops=flops)
+    return dw
 
 
 def gemm_rows(x, w, K, n_out, chunks=None):
@@ -1036,7 +957,6 @@ class _EdgeChainTrain(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feature, idx, edge_convs, lattice, *params):
         ctx.packs = _PACKS
-        ctx.side = _on_side(3)
         x = feature.detach().contiguous()
         N, cin = x.shape
         idx = idx.contiguous()
@@ -1083,7 +1003,7 @@ class _EdgeChainTrain(torch.autograd.Function):
                 into = None
                 if t1 is not None and t2 is not None and t2.data_ptr() == t1.data_ptr() + 4 * C * K:
                     into = torch.as_strided(t1, (2 * C, K), (K, 1))
-                dw = rows_wgrad(grad_le, X, 2 * C, K, into=into, side=ctx.side)
+                dw = rows_wgrad(grad_le, X, 2 * C, K, into=into)
                 dX = gemm_rows(grad_le, wcat, 2 * C, K, chunks)                            # (N, K)
                 if col == 0:
                     gx = dX
@@ -1129,7 +1049,6 @@ class _MLPTrain(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, shared, *params):
         ctx.packs = _PACKS
-        ctx.side = _on_side(3)
         X = x.detach()
         if X.stride(1) != 1:
             X = X.contiguous()
@@ -1164,7 +1083,7 @@ class _MLPTrain(torch.autograd.Function):
                 dZ, dgamma, dbeta = rows_bn_backward(g, Z, rows, cout, 1, N, 1, True, into=into)
                 tw = _grad_target(blk.conv.weight)
                 dw = rows_wgrad(dZ, X, cout, K, x_affine=affine, x_rows_per_stat=N,
-                                into=None if tw is None else tw.view(cout, K), side=ctx.side)
+                                into=None if tw is None else tw.view(cout, K))
                 g = gemm_rows(dZ, blk.conv.weight.detach().reshape(cout, K), cout, K,
                               _packed("rows", blk.conv.weight))                           # gradient w.r.t. act(X)
                 gparams = [None if dw is None else dw.reshape(blk.conv.weight.shape), dgamma, dbeta] + gparams

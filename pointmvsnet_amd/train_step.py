@@ -241,7 +241,7 @@ class TrainStep(object):
             losses = self.loss_fn(preds, batch, is_flow)
             total = _total(losses)
             total.backward()
-        join_fork_streams()                                        # the flow tower's backward ran beside the coarse stage's
+            join_fork_streams()                                    # the flow tower's backward ran beside the coarse stage's
         self.finish()
         return total.detach(), losses, preds
 
@@ -307,7 +307,7 @@ class GraphedTrainStep(object):
             losses = self.t.loss_fn(preds, labels, self.is_flow)
             total = _total(losses)
             total.backward()
-        join_fork_streams()
+            join_fork_streams()
         return total.detach(), {k: v.detach() for k, v in losses.items()}, {k: v.detach() for k, v in preds.items()}
 
     def __call__(self, batch):

@@ -697,6 +697,28 @@ def test_train_step_gradient_is_bit_reproducible(dev, cfg):
     assert torch.equal(grads[0], grads[1]) and float(grads[0].abs().sum()) > 0
 
 
+def test_direct_grads_backward_is_complete_without_the_join(dev):
+    """forward + loss + backward() under train_ops.direct_grads() and NOTHING else -- no model.join_fork_streams(), which
+    TrainStep calls to deal the weight gradients that wait for the end of the backward to two streams -- leaves the same
+    698 936 gradient bits in the bucket as TrainStep: the block issues what is still queued when it is left."""
+    from pointmvsnet_amd import train_ops, train_step
+    data, img_scales, inter_scales = synthetic.make_config("tiny", train_intrinsics=True)
+    batch = _to(data, dev)
+    batch["gt_depth_img"] = synthetic.make_gt_depth(data).to(dev)
+    step = train_step.TrainStep(_model(dev))
+    step(batch, img_scales, inter_scales)
+    want = step.bucket.flat.detach().clone()
+    step = train_step.TrainStep(_model(dev))
+    step.model.train()
+    step.bucket.zero_()
+    with train_ops.direct_grads():
+        preds = step.model(batch, img_scales, inter_scales, isFlow=True, isTest=False)
+        train_step._total(step.loss_fn(preds, batch, True)).backward()
+    torch.cuda.synchronize()
+    assert len(train_ops.wgrad_queue) == 0
+    assert torch.equal(step.bucket.flat, want) and float(want.abs().sum()) > 0
+
+
 @pytest.mark.parametrize("cfg", ["tiny"])
 def test_graphed_train_step_matches_the_eager_step(dev, cfg):
     """(tests/test_gpu_zz_train_cfg4.py calls this with "cfg4": the captured step bench.py times, at its own size.)

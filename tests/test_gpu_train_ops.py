@@ -117,9 +117,9 @@ def test_swapped_operand_weight_gradient_in_the_batched_reduce(dev, N, Cout, Cin
     """Stride-1 layers with <= 8 output channels run pf_conv_wgrad_f32 with the operands swapped; inside the step the
     (Cin, Cout, reversed taps) partials are put into nn.ConvNd's order by pf_wgrad_reduce_batch_f32 (swapped), ADDED into the
     gradient slot, in one launch with a plain layer's partials.  Against float64 autograd, and against PF_WGRAD_SWAP=0.
-    ``late``: the layers are queued until the node returns (0: _reduce_flush) or until the end of the backward (2, the
-    default: flush_late) and issued together by pf_conv_wgrad_batch_f32 either way."""
-    monkeypatch.setattr(train_ops, "WGRAD_LATE", late)
+    ``late``: the layers are queued until the end of the backward (2: computed on the stream direct_grads was entered on,
+    issued by flush_late) or until the node returns (0: computed on another stream, issued there by the node-return
+    flush) and go out together through pf_conv_wgrad_batch_f32 either way."""
     nd = len(sp)
     conv = F.conv2d if nd == 2 else F.conv3d
     x = _seeded((N, Cin) + sp, dev, 11)
@@ -130,27 +130,63 @@ def test_swapped_operand_weight_gradient_in_the_batched_reduce(dev, N, Cout, Cin
     w2 = torch.zeros((16, 16) + (3,) * nd, dtype=torch.float64, device=dev, requires_grad=True)
     conv(x.double(), w, None, 1, 1).backward(dy.double())
     conv(x2.double(), w2, None, 1, 1).backward(dy2.double())
+    queue = train_ops.wgrad_queue
     outs = {}
     for swap in (1, 0):
         monkeypatch.setattr(train_ops, "WGRAD_SWAP", swap)
         slot = torch.full(w.shape, 0.25, dtype=torch.float32, device=dev)      # "into": the bucket's slot, dw is ADDED
         slot2 = torch.full(w2.shape, -0.5, dtype=torch.float32, device=dev)
+        torch.cuda.synchronize()                                               # (the other stream reads all of these)
         with train_ops.direct_grads(True):
-            assert train_ops.conv_wgrad(dy, x, (3,) * nd, 1, (1,) * nd, into=slot) is None
-            assert train_ops.conv_wgrad(dy2, x2, (3,) * nd, 1, (1,) * nd, into=slot2) is None
-            queue = train_ops._LATE["reduce"] if late else train_ops._REDUCE_PENDING
-            assert len(queue) == 2 and bool(queue[0][6]) == bool(swap)
-            if late:
-                assert not train_ops._REDUCE_PENDING and len(train_ops._LATE["wgrad"]) == 2
-                train_ops.flush_late()
-            else:
-                train_ops._reduce_flush()
-            assert not train_ops._LATE["reduce"] and not train_ops._REDUCE_PENDING and not train_ops._WGRAD_DEFERRED
+            with torch.cuda.stream(torch.cuda.current_stream() if late else torch.cuda.Stream()):
+                assert train_ops.conv_wgrad(dy, x, (3,) * nd, 1, (1,) * nd, into=slot) is None
+                assert train_ops.conv_wgrad(dy2, x2, (3,) * nd, 1, (1,) * nd, into=slot2) is None
+                waiting, other = (queue.late, queue.node) if late else (queue.node, queue.late)
+                assert len(waiting) == 2 and not other and bool(waiting[0].swapped) == bool(swap)
+                if late:
+                    train_ops.flush_late()
+                else:
+                    queue.flush_node()
+                assert not queue.late and not queue.node
+        torch.cuda.synchronize()
         outs[swap] = (slot - 0.25, slot2 + 0.5)
     e1, e0, e2 = _rel(outs[1][0], w.grad), _rel(outs[0][0], w.grad), _rel(outs[1][1], w2.grad)
     report("conv_wgrad_swapped_%dd_%dto%d" % (nd, Cin, Cout), rel=e1, rel_plain=e0, rel_neighbour=e2)
     assert e1 < 2e-5 and e0 < 2e-5 and e2 < 2e-5, (e1, e0, e2)
     assert torch.equal(outs[1][1], outs[0][1])                     # the plain neighbour does not notice
+
+
+def test_direct_grads_issues_or_drops_every_queued_weight_gradient(dev):
+    """Leaving direct_grads() normally issues what is still queued (the same bits as the explicit flush_late()); leaving
+    it through an exception drops the queue, touches no slot and lets the next block start; outside it ``into`` raises."""
+    x, dy = _seeded((2, 16, 24, 40), dev, 21), _seeded((2, 8, 24, 40), dev, 22)
+    queue = train_ops.wgrad_queue
+
+    def add(slot):
+        assert train_ops.conv_wgrad(dy, x, (3, 3), 1, (1, 1), into=slot) is None
+        assert len(queue) == 1
+
+    slots = [torch.full((8, 16, 3, 3), 0.25, dtype=torch.float32, device=dev) for _ in range(3)]
+    with train_ops.direct_grads(True):
+        add(slots[0])
+        train_ops.flush_late()
+    with train_ops.direct_grads(True):
+        add(slots[1])
+    assert len(queue) == 0
+    torch.cuda.synchronize()
+    assert torch.equal(slots[0], slots[1]) and not torch.equal(slots[0], slots[2])
+    with pytest.raises(ZeroDivisionError):
+        with train_ops.direct_grads(True):
+            add(slots[2])
+            raise ZeroDivisionError
+    assert len(queue) == 0
+    with train_ops.direct_grads(True):
+        pass
+    torch.cuda.synchronize()
+    assert bool((slots[2] == 0.25).all())
+    with pytest.raises(RuntimeError):
+        train_ops.conv_wgrad(dy, x, (3, 3), 1, (1, 1), into=slots[2])
+    assert len(queue) == 0 and bool((slots[2] == 0.25).all())
 
 
 @pytest.mark.parametrize("Cin,Cout,sp", [(64, 32, (2, 4, 6)), (32, 16, (4, 8, 12)), (16, 8, (8, 8, 12))])
