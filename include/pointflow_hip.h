@@ -614,6 +614,37 @@ int pf_cloud_obs_mask_f32(const float* points, int64_t n, const unsigned char* m
 int pf_cloud_above_plane_f32(const float* points, int64_t n, float a, float b, float c, float d, unsigned char* above,
                              void* stream);
 
+/* ---- cleaning a fused cloud: k-nearest statistics and a voxel-grid merge (csrc/cloud_filter.hip) -------------------
+ * The specification is this project's own (pointmvsnet_amd/cloud_filter.py).  The searches take the
+ * sorted grid of pf_cloud_cell_keys_f32 / pf_cloud_pack_f32 above over the cloud itself, with plain index tags (hashed = 0)
+ * and any edge.  d2(i, j) = (dx*dx + dy*dy) + dz*dz in float32; the neighbours of i are the points j != i by index (tag).
+ * Both searches visit the cubes of radius r = 1, 2, .. cells around a point's cell until a ring is final: when it decides
+ * the result -- see below -- or when (r - 0.05) * edge >= radius, the cube then holding everything within radius.
+ * pf_cloud_knn_stats_f32: per point i, with a_1 <= a_2 <= ... the c = min(k, number of neighbours with d2 < radius2)
+ *   smallest such d2: mean[i] = (((sqrtf(a_1) + sqrtf(a_2)) + ...) + float(k - c) * radius) / float(k), or radius itself
+ *   when c = 0; count[i] = c (count may be NULL).  Final also when the k-th best is <= ((r - 0.05) * edge)^2.
+ *   1 <= k <= PF_CLOUD_MAX_K; radius2 is the caller's float32 product radius * radius.
+ * pf_cloud_radius_count_f32: count[i] = min(limit, number of neighbours with d2 < radius2); final also when limit are
+ *   found.  1 <= limit <= PF_CLOUD_MAX_K.
+ * pf_cloud_voxel_keys_f32: keys (n) = cx << 42 | cy << 21 | cz with c = floor((p - o) * inv) per axis in float32, clamped to
+ *   [0, n_axis - 1]; inv is the caller's float32 reciprocal of the voxel edge, n_axis <= PF_CLOUD_MAX_CELLS.
+ * pf_cloud_voxel_reduce_f32: the caller sorts the keys STABLY; order (n) is that permutation and starts (m + 1) the first
+ *   sorted slot of each of the m voxels, starts[m] = n.  Row s of the outputs, from the points order[starts[s] ..
+ *   starts[s+1]) in that (ascending index) order: out_points = float32(float64 sum / count); out_colors (uint8, with colors)
+ *   = (2 * sum + count) / (2 * count) per channel in integers; out_normals (with normals) = the float64 sum divided by its
+ *   float64 length, rounded to float32, (0, 0, 0) when the length is 0; out_counts (int32, may be NULL); inverse (n, may be
+ *   NULL)[order[t]] = s.  colors / out_colors and normals / out_normals are given or NULL together. */
+#define PF_CLOUD_MAX_K 32
+int pf_cloud_knn_stats_f32(const void* packed, const int64_t* keys, int64_t n, int nx, int ny, int nz, float edge, int k,
+                           float radius, float radius2, float* mean, int* count, void* stream);
+int pf_cloud_radius_count_f32(const void* packed, const int64_t* keys, int64_t n, int nx, int ny, int nz, float edge,
+                              int limit, float radius, float radius2, int* count, void* stream);
+int pf_cloud_voxel_keys_f32(const float* points, int64_t n, float ox, float oy, float oz, float inv, int nx, int ny, int nz,
+                            int64_t* keys, void* stream);
+int pf_cloud_voxel_reduce_f32(const float* points, const unsigned char* colors, const float* normals, const int64_t* order,
+                              const int64_t* starts, int64_t n, int64_t m, float* out_points, unsigned char* out_colors,
+                              float* out_normals, int* out_counts, int64_t* inverse, void* stream);
+
 /* ---- rendering a point cloud into depth maps: a z-buffer point splat (csrc/cloud_render.hip) -----------------------
  * The inverse of the fusers' back-projection, which the reference does not have (it scores depth maps against ground-truth
  * depth maps; DTU's test scans ship a ground-truth cloud).  The specification is this project's own

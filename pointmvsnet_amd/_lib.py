@@ -120,6 +120,10 @@ PROTOTYPES = {
     "pf_cloud_nn_wave_f32": ([_vp, _vp, _i64, _i64, _vp, _vp, _i64, _f, _f, _f, _f, _i, _i, _i, _f, _vp, _vp, _vp], _i),
     "pf_cloud_obs_mask_f32": ([_vp, _i64, _vp, _i, _i, _i, _f, _f, _f, _f, _vp, _vp], _i),
     "pf_cloud_above_plane_f32": ([_vp, _i64, _f, _f, _f, _f, _vp, _vp], _i),
+    "pf_cloud_knn_stats_f32": ([_vp, _vp, _i64, _i, _i, _i, _f, _i, _f, _f, _vp, _vp, _vp], _i),
+    "pf_cloud_radius_count_f32": ([_vp, _vp, _i64, _i, _i, _i, _f, _i, _f, _f, _vp, _vp], _i),
+    "pf_cloud_voxel_keys_f32": ([_vp, _i64, _f, _f, _f, _f, _i, _i, _i, _vp, _vp], _i),
+    "pf_cloud_voxel_reduce_f32": ([_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp], _i),
     "pf_cloud_splat_f32": ([_vp, _i64, _vp, _i, _i, _i, _i, _f, _f, _vp, _vp], _i),
     "pf_cloud_zbuf_decode": ([_vp, _i, _i, _i, _vp, _vp, _vp], _i),
     "pf_preprocess_resize_u8": ([_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp], _i),

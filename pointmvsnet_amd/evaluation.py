@@ -54,10 +54,13 @@ def last_unfinished_queries():
     return _last_unfinished
 
 
-def _check_points(points, what):
+def _check_points(points, what, gpu=True):
+    """The rules for a cloud.  ``gpu=False`` leaves the device check to the caller (cloud_filter.py judges its other
+    arguments first, so that their ``ValueError`` needs no GPU)."""
     if not isinstance(points, torch.Tensor):
         raise TypeError("%s: expected a torch tensor" % what)
-    _lib.require_gpu(points)
+    if gpu:
+        _lib.require_gpu(points)
     if points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float32:
         raise ValueError("%s: points must be (N, 3) float32" % what)
     if points.shape[0] > MAX_POINTS:

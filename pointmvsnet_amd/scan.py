@@ -41,6 +41,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .cloud_filter import clean_cloud
 from .fusion import fuse_depth_maps
 from .geometric import geometric_filter
 from .normals import depth_normals
@@ -177,6 +178,7 @@ class ScanAccumulator(object):
         self.keep_images = keep_images
         self._seen = [False] * self.view_num
         self._depth = self._flow = self._init = self._images = None
+        self.last_clean_report = None
         self._with_image = 0
         self._K = np.zeros((self.view_num, 3, 3))
         self._E = np.zeros((self.view_num, 4, 4))
@@ -277,26 +279,38 @@ class ScanAccumulator(object):
         return depth_normals(self.filtered(), K, E, step=step, rel_jump=rel_jump)
 
     def fuse(self, disp_threshold=0.12, num_consistent=3, depth_min=1e-3, depth_max=1e5, method="disparity",
-             with_normals=False, normal_step=1, normal_rel_jump=0.01, **kwargs):
+             with_normals=False, normal_step=1, normal_rel_jump=0.01, clean=None, **kwargs):
         """``(points (N, 3) float32, colours (N, 3) uint8 or None)``: with ``method="disparity"`` through
         ``fuse_depth_maps``; with ``method="roundtrip"`` the cloud of ``geometric()`` (``disp_threshold`` is not used;
         ``kwargs``: ``sources``, ``pix_threshold``, ``rel_depth_threshold``).  With ``with_normals`` a third value, the
-        points' normals (N, 3) float32 as the method's fuser defines them (``normals.py``)."""
+        points' normals (N, 3) float32 as the method's fuser defines them (``normals.py``).  ``clean``: a dict of
+        ``cloud_filter.clean_cloud``'s keyword arguments, applied to the cloud of either method with its colours and
+        normals carried through; its report is kept as ``last_clean_report`` (None after a call without ``clean``).  ``None``
+        leaves the fuser's cloud as it is."""
         if method not in ("disparity", "roundtrip"):
             raise ValueError("ScanAccumulator.fuse: unknown method %r (disparity or roundtrip)" % (method,))
+        if clean is not None and not isinstance(clean, dict):
+            raise TypeError("ScanAccumulator.fuse: clean must be a dict of clean_cloud's keyword arguments or None")
         self._require_complete("fuse")
         normal_kwargs = {}
         if with_normals:
             normal_kwargs = {"with_normals": True, "normal_step": normal_step, "normal_rel_jump": normal_rel_jump}
         if method == "roundtrip":
             kwargs.update(normal_kwargs)
-            return self.geometric(num_consistent=num_consistent, depth_min=depth_min, depth_max=depth_max,
-                                  **kwargs)[3:6 if with_normals else 5]
-        if kwargs:
-            raise TypeError("ScanAccumulator.fuse: %s belong to method=\"roundtrip\"" % ", ".join(sorted(kwargs)))
-        K, E = self.cameras()
-        return fuse_depth_maps(self.filtered(), K, E, images=self.images(), disp_threshold=disp_threshold,
-                               num_consistent=num_consistent, depth_min=depth_min, depth_max=depth_max, **normal_kwargs)
+            fused = self.geometric(num_consistent=num_consistent, depth_min=depth_min, depth_max=depth_max,
+                                   **kwargs)[3:6 if with_normals else 5]
+        else:
+            if kwargs:
+                raise TypeError("ScanAccumulator.fuse: %s belong to method=\"roundtrip\"" % ", ".join(sorted(kwargs)))
+            K, E = self.cameras()
+            fused = fuse_depth_maps(self.filtered(), K, E, images=self.images(), disp_threshold=disp_threshold,
+                                    num_consistent=num_consistent, depth_min=depth_min, depth_max=depth_max, **normal_kwargs)
+        self.last_clean_report = None
+        if clean is None:
+            return fused
+        points, colours, normals, self.last_clean_report = clean_cloud(
+            fused[0], fused[1], fused[2] if with_normals else None, **clean)
+        return (points, colours) + ((normals,) if with_normals else ())
 
     def depth_errors(self, gt_points, thresholds, splat=1, filtered=True):
         """``render.depth_map_errors`` of the accumulated depth maps -- ``filtered()``, or the raw ``predictions()[0]`` with
@@ -309,7 +323,7 @@ class ScanAccumulator(object):
                                 thresholds)
 
     def write_ply(self, path, **fuse_kwargs):
-        """Fuse (``fuse_kwargs``: those of ``fuse``, ``method`` and ``with_normals`` among them) and write the cloud to
+        """Fuse (``fuse_kwargs``: those of ``fuse``, ``method``, ``with_normals`` and ``clean`` among them) and write the cloud to
         ``path``; returns what ``fuse`` returned: ``(points, colours)`` and, ``with_normals``, the normals."""
         fused = self.fuse(**fuse_kwargs)
         write_ply(path, fused[0].cpu().numpy(), None if fused[1] is None else fused[1].cpu().numpy(),
@@ -321,7 +335,7 @@ def reconstruct_scan(model, batches, img_scales=(0.125, 0.25, 0.5), inter_scales
                      fuse_kwargs=None, **accumulator_kwargs):
     """Run ``model`` on every ``data_batch`` of one scan (any iterable; one view as the reference each), accumulate the
     views and fuse them: ``(points, colours, accumulator)``, or ``(points, colours, normals, accumulator)`` when
-    ``fuse_kwargs`` asks ``with_normals``.
+    ``fuse_kwargs`` asks ``with_normals``.  A ``clean`` entry of ``fuse_kwargs`` cleans the cloud (``ScanAccumulator.fuse``).
 
     A ``torch.nn.Module`` is called as the evaluation forward, ``model(data_batch, img_scales, inter_scales, isFlow=True,
     isTest=True)`` under ``torch.no_grad()``; anything else (a ``GraphedForward``) as ``model(data_batch)``.  ``view_num``

@@ -4,6 +4,7 @@ preprocessing, the network, the batched confidence filter, the fusion and, optio
     python tools/reconstruct_scan.py --root DTU --scan 9 --weights model.pth --out scan9.ply \
         [--mode LANCZOS4] [--init-prob-threshold 0.2] [--flow-prob-threshold 0.1] [--name flow2] \
         [--fusion roundtrip --num-src 10 --save-depth DIR] [--normals [--normal-step 2]] \
+        [--voxel 0.2] [--outlier-radius 2.0 [--outlier-k 16] [--outlier-std 2.0] [--min-neighbors 4]] \
         [--gt stl009_total.ply --obs-mask ObsMask9_10.mat --plane Plane9.mat [--depth-errors --splat 1]]
 
 ``--weights`` is a ``torch.load``-able file: its ``"model"`` entry if it has one, a leading ``module.`` stripped from the
@@ -11,9 +12,14 @@ keys.  ``--fusion roundtrip`` replaces the disparity fusion by the round-trip co
 (pointmvsnet_amd/geometric.py) against the first ``--num-src`` views that ``Cameras/pair.txt`` lists for every view (0: all
 other views); ``--save-depth DIR`` writes that filter's averaged depth map and mask of every view as ``%08d_geo.pfm`` and
 ``%08d_geo_mask.pfm``.  ``--normals`` writes the oriented cloud, ``x y z nx ny nz [red green blue]`` per vertex: normals from
-the depth maps (pointmvsnet_amd/normals.py) with finite differences ``--normal-step`` pixels wide.  Prints one JSON line: the
-number of points, with ``--normals`` the number of them whose normal is undefined, the kept share per view and, with ``--gt``,
-the dict of ``evaluate_point_cloud``.  With ``--gt --depth-errors`` a second JSON line follows: the ground-truth cloud rendered
+the depth maps (pointmvsnet_amd/normals.py) with finite differences ``--normal-step`` pixels wide.  ``--voxel`` and
+``--outlier-radius`` clean the fused cloud before it is written (pointmvsnet_amd/cloud_filter.py, ``clean_cloud``): a voxel
+merge at that edge, then, inside that radius, the radius test with ``--min-neighbors`` (if given) and the statistical test
+over ``--outlier-k`` neighbours at ``--outlier-std`` standard deviations (a negative value turns it off); colours and normals
+are carried through.  Prints one JSON line: the
+number of points, with ``--normals`` the number of them whose normal is undefined, the kept share per view, with cleaning its
+``report`` (the point counts after each step) and, with ``--gt``,
+the dict of ``evaluate_point_cloud`` -- with cleaning of the cleaned cloud, and of the cloud before it as ``score_before_cleaning``.  With ``--gt --depth-errors`` a second JSON line follows: the ground-truth cloud rendered
 into every view (pointmvsnet_amd/render.py, ``--splat`` pixels around each projection) and ``depth_map_errors`` of the raw and of the
 filtered depth maps against it, per view and in total, at thresholds of 1 and 3 times the reference view's depth interval
 scaled for ``--name`` as ``PointMVSNetMetric`` scales it (coarse 1, flow1 0.75, flow2 0.375).
@@ -71,6 +77,11 @@ def main():
     ap.add_argument("--save-depth", default=None, help="folder for the round-trip filter's %%08d_geo.pfm / %%08d_geo_mask.pfm")
     ap.add_argument("--normals", action="store_true", help="write nx ny nz per vertex (normals from the depth maps)")
     ap.add_argument("--normal-step", type=int, default=1, help="--normals: the finite-difference baseline in pixels")
+    ap.add_argument("--voxel", type=float, default=None, help="merge the fused points of every voxel of this edge")
+    ap.add_argument("--outlier-radius", type=float, default=None, help="search radius of the outlier tests (none: no test)")
+    ap.add_argument("--outlier-k", type=int, default=16, help="statistical test: neighbours per point")
+    ap.add_argument("--outlier-std", type=float, default=2.0, help="statistical test: standard deviations kept (< 0: off)")
+    ap.add_argument("--min-neighbors", type=int, default=None, help="radius test: neighbours needed inside --outlier-radius")
     ap.add_argument("--name", default="flow2")
     ap.add_argument("--num-view", type=int, default=5)
     ap.add_argument("--height", type=int, default=960)
@@ -88,7 +99,7 @@ def main():
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args()
     import torch
-    from pointmvsnet_amd import evaluation, geometric, scan, synthetic
+    from pointmvsnet_amd import cloud_filter, evaluation, geometric, scan, synthetic
     from pointmvsnet_amd.dataset import DTUDataset
     from pointmvsnet_amd.model import PointMVSNet
     from pointmvsnet_amd.utils import io
@@ -115,11 +126,24 @@ def main():
         fuse_kwargs=fuse_kwargs, name=args.name,
         mode=args.mode, init_prob_threshold=args.init_prob_threshold, flow_prob_threshold=args.flow_prob_threshold)
     normals = normals[0] if normals else None
+    clean = {}
+    if args.voxel is not None:
+        clean["voxel"] = args.voxel
+    if args.outlier_radius is not None:
+        clean.update(max_radius=args.outlier_radius, k=args.outlier_k, min_neighbors=args.min_neighbors,
+                     std_ratio=args.outlier_std if args.outlier_std >= 0 else None)
+    elif args.min_neighbors is not None:
+        ap.error("--min-neighbors needs --outlier-radius")
+    raw_points = points
+    if clean:                                                # what ScanAccumulator.fuse(clean=...) does; here both clouds are kept
+        points, colours, normals, report = cloud_filter.clean_cloud(points, colours, normals, **clean)
     io.write_ply(args.out, points.cpu().numpy(), None if colours is None else colours.cpu().numpy(),
                  None if normals is None else normals.cpu().numpy())
     filtered, kept = acc.filtered(return_kept=True)
     out = {"scan": args.scan, "views": len(dataset), "mode": args.mode, "fusion": args.fusion, "points": int(points.shape[0]), "out": args.out,
            "kept_share_per_view": [k / float(filtered[0].numel()) for k in kept.cpu().tolist()]}
+    if clean:
+        out["report"] = report
     if normals is not None:
         out["normals_undefined"] = int((normals == 0).all(dim=1).sum())
     if args.save_depth:
@@ -140,6 +164,8 @@ def main():
             kw.update(plane=io.load_dtu_plane(args.plane))
         gt = torch.from_numpy(io.load_ply_points(args.gt)).to(dev)
         out["score"] = evaluation.evaluate_point_cloud(points, gt, **kw)
+        if clean:
+            out["score_before_cleaning"] = evaluation.evaluate_point_cloud(raw_points, gt, **kw)
     print(json.dumps(out))
     if args.gt and args.depth_errors:
         interval = float(dataset[0]["cam_params_list"][0, 1, 3, 1]) * INTERVAL_SCALE.get(args.name, 1.0)
