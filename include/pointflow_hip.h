@@ -180,21 +180,15 @@ int pf_stat_blocks(int G, int Ng);
 /* Blocks per group used by pf_pointwise_gemm_f32 (128-point tiles); its partials are (G, Tg, Nc, 2). */
 int pf_gemm_blocks(int G, int Ng);
 
-/* BatchNorm (training mode) statistics -> affine.  Reduces partials (G, T, pcols, 2) over the T blocks
+/* BatchNorm (training mode) statistics -> affine, one job.  Reduces partials (G, T, pcols, 2) over the T blocks
  * of `groups_per_stat` consecutive groups, columns [col0, col0+C):  mean = S/count,
  * var = SS/count - mean^2 (biased, used to normalise), scale = gamma*rsqrt(var+eps),
  * shift = beta - mean*scale; written to scale/shift[s*ld_affine + c].  When running_mean != NULL the
  * running statistics are updated S times in group order exactly like S successive nn.BatchNorm
  * calls (momentum, unbiased variance with n = unbias_n; reference runs BN in train mode at test time,
- * test.py:58).  count = elements per STAT group behind the sums. */
-int pf_bn_finalize_f32(const double* partials, int T, int pcols, int col0, int C, double count,
-                       double unbias_n, const float* gamma, const float* beta, float* running_mean,
-                       float* running_var, float momentum, float eps, int G, int groups_per_stat,
-                       float* scale, float* shift, int ld_affine, void* stream);
-
-/* The same, for 1..32 independent jobs in one launch (e.g. the central and the difference half of an
- * EdgeConv BatchNorm, reference networks.py:33-36).  Fields = the arguments of pf_bn_finalize_f32; the
- * jobs must write disjoint scale/shift/running-stat ranges. */
+ * test.py:58).  count = elements per STAT group behind the sums.
+ * pf_bn_finalize_jobs_f32 runs 1..32 independent jobs in one launch (e.g. the central and the difference half of an
+ * EdgeConv BatchNorm, reference networks.py:33-36); the jobs must write disjoint scale/shift/running-stat ranges. */
 typedef struct pf_bn_job {
   const double* partials;
   int32_t T, pcols, col0, C;
@@ -266,40 +260,25 @@ int pf_edge_apply_f32(const float* LE, int64_t ldle, int C, const int64_t* idx, 
  * grad_y (G*Ng, ldg) point-major: [G_central C | G_diff C] (concat) or [G_diff C]; scale/shift/mean/invstd
  * rows (S, ld_affine) in the same column order (scale = gamma*invstd, shift = beta - mean*scale of the
  * forward; mean / invstd = its batch statistics).
- *   reduce: partials (G, pf_stat_blocks(G,Ng), cols, 2) float64, cols = 2C | C, per column
- *           (sum g, sum g*xhat) with g = [u > 0] * G / k (central half: [u > 0] * G) -> dbeta, dgamma
- *   apply : grad_le (G*Ng, ldle) = [dl | de]; c1 = dbeta/M, c2 = dgamma/M rows (S, ld_affine), M = elements
- *           behind the statistics of that column (diff: gps*Ng*k; central: gps*Ng).  With inv_order /
- *           inv_start (pf_knn_inverse below) de is gathered over the inverted lists, columns [0, 2C) of every row
- *           are written with plain stores and the result is bit-reproducible; with NULL grad_le is zeroed by
- *           the call and the de rows are accumulated with float atomics (as the reference's scatter).
- * C in {32, 64}. */
-int pf_edge_backward_reduce_f32(const float* LE, int64_t ldle, int C, const int64_t* idx, int k, int G, int Ng,
-                                const float* grad_y, int64_t ldg, const float* scale, const float* shift,
-                                const float* mean, const float* invstd, int ld_affine, int groups_per_stat,
-                                int concat, double* partials, void* stream);
-int pf_edge_backward_apply_f32(const float* LE, int64_t ldle, int C, const int64_t* idx, int k, int G, int Ng,
-                               const float* grad_y, int64_t ldg, const float* scale, const float* shift,
-                               const float* mean, const float* invstd, const float* c1, const float* c2,
-                               int ld_affine, int groups_per_stat, int concat, float* grad_le,
-                               const uint32_t* inv_order, const uint32_t* inv_start, void* stream);
-
-/* The same backward in TWO walks over the neighbourhoods instead of three (round 6).  dl = -sum_j dd_j is linear in
- * (c1, c2): dl = -a * ((sum_j g_j - k * c1) - c2 * sum_j xhat_j), so the reduce pass can leave every point's own sums
- * behind and nobody has to walk the forward lists again.
- *   sums  : pf_edge_backward_reduce_f32 + grad_le (G*Ng, ldle): row n = [sum_j g_j (C) | sum_j xhat_j (C)].
+ * Two walks over the neighbourhoods.  With g = [u > 0] * G / k (central half: [u > 0] * G), c1 = dbeta/M, c2 = dgamma/M
+ * (M = elements behind the statistics of that column: gps*Ng*k for the difference half, gps*Ng for the central one),
+ * dl = -sum_j dd_j is linear in (c1, c2): dl = -a * ((sum_j g_j - k * c1) - c2 * sum_j xhat_j), so the first walk can
+ * leave every point's own sums behind and the forward lists are walked once.
+ *   sums  : partials (G, pf_stat_blocks(G,Ng), cols, 2) float64, cols = 2C | C, per column (sum g, sum g*xhat)
+ *           -> dbeta, dgamma; and grad_le (G*Ng, ldle): row n = [sum_j g_j (C) | sum_j xhat_j (C)].
  *           grad_acc (G*Ng, ld_acc) or NULL: a second upstream gradient in grad_y's column order (the next layer's data
  *           gradient, model.py:209-216's chain); the pass uses grad_y + grad_acc and stores that sum back into grad_acc,
  *           which the caller hands to `finish` as its grad_y (one element-wise launch less per layer).
- *   finish: (after pf_edge_backward_coeffs_f32) the gather over the inverted lists (inv_order / inv_start are required)
- *           writes de AND turns the row's sums into dl (+ the central half of a concat layer): grad_le = [dl | de], plain
- *           stores, bit-reproducible.  dl differs from pf_edge_backward_apply_f32's in float32 rounding only (the sum is
- *           taken before the coefficients are applied instead of after).
+ *   finish: (after pf_edge_backward_coeffs_f32: c1, c2 rows (S, ld_affine)) the gather over the inverted lists
+ *           (inv_order / inv_start of pf_knn_inverse below) writes de -- point m sums dd over the pairs that gathered
+ *           it, in ascending pair order -- AND turns the row's sums into dl (+ the central half of a concat layer):
+ *           grad_le = [dl | de], columns [0, 2C) of every row written with plain stores, bit-reproducible (the
+ *           reference's scatter uses float atomics).
+ * C in {32, 64}.
  * plane: points per lattice plane (H*W of the D x H x W lattice the neighbours come from) or 0 = unknown -- a hint for
  * the XCD-aware block order only (each of the 8 L2s serves a band of pixel rows in every plane instead of every eighth
  * tile of the whole lattice); results do not depend on it.  pf_edge_stats_f32 / pf_edge_apply_f32 take the same hint as
- * (lat_ks 0, lat_h, lat_w) when they are given an index tensor instead of window codes.
- * Replaces networks.py:18-45's autograd graph like the three-pass form above. */
+ * (lat_ks 0, lat_h, lat_w) when they are given an index tensor instead of window codes. */
 int pf_edge_backward_sums_f32(const float* LE, int64_t ldle, int C, const int64_t* idx, int k, int G, int Ng,
                               const float* grad_y, int64_t ldg, const float* scale, const float* shift,
                               const float* mean, const float* invstd, int ld_affine, int groups_per_stat, int concat,
@@ -323,10 +302,9 @@ int pf_edge_backward_coeffs_f32(const double* partials, int G, int T, int cbn, i
 /* The inverse of a neighbour index tensor idx (G, Ng, k) (csrc/knn_inverse.hip): order (G*Ng*k) = the pair ids
  * p = (g*Ng + n)*k + j grouped by their target row g*Ng + clamp(idx[p], 0, Ng-1); start (G*Ng + 1): the pairs
  * that gather row m are order[start[m] .. start[m+1]), in ascending p.  With (inv_order, inv_start)
- * pf_edge_backward_apply_f32 computes the de rows as a GATHER over those lists -- plain stores in a fixed summation
- * order, bit-reproducible -- instead of the float atomics of the reference's scatter
- * (functions/csrc/gather_knn_kernel.cu:50-89); NULL keeps the atomics.  One inversion serves every layer that
- * shares idx.  A counting sort in kernel launches only (no memset / memcpy nodes, no library call: capturable in a
+ * pf_edge_backward_finish_f32 and pf_gather_knn_backward_* compute their scatter as a GATHER over those lists -- plain
+ * stores in a fixed summation order, bit-reproducible -- instead of the float atomics of the reference's scatter
+ * (functions/csrc/gather_knn_kernel.cu:50-89).  One inversion serves every layer that shares idx.  A counting sort in kernel launches only (no memset / memcpy nodes, no library call: capturable in a
  * hipGraph).  workspace: pf_knn_inverse_workspace(G, Ng, k) bytes of device scratch. */
 int64_t pf_knn_inverse_workspace(int G, int Ng, int k);
 int pf_knn_inverse(const int64_t* idx, int k, int G, int Ng, uint32_t* order, uint32_t* start, void* workspace,
@@ -335,7 +313,7 @@ int pf_knn_inverse(const int64_t* idx, int k, int G, int Ng, uint32_t* order, ui
 /* ---- train-mode BatchNorm for the conv stacks around the path (ImageConv / VolumeConv) ----------
  * x (N, C, S) contiguous (NCHW / NCDHW with S = spatial size).  pf_channel_stats_f32 writes float64
  * partial (sum, sum of squares) per (sample, block, channel): partials (N, pf_norm_blocks(S), C, 2), the
- * layout pf_bn_finalize_f32 reduces (G = N samples; groups_per_stat samples pooled per statistic, e.g.
+ * layout pf_bn_finalize_jobs_f32 reduces (G = N samples; groups_per_stat samples pooled per statistic, e.g.
  * the batch of one reference conv call, nn/conv.py:29-35).  pf_channel_affine_f32 applies
  * y = x*scale[s,c] + shift[s,c] (s = n / samples_per_stat) with optional ReLU; y may alias x. */
 int pf_norm_blocks(int64_t S);
@@ -362,7 +340,7 @@ int pf_channel_bn_apply2_f32(const float* x1, const double* partials1, int T1, c
 /* Statistics + finalize + normalise in ONE launch for small tensors (one 1024-thread block per channel walks
  * the stat groups in order): y = act(BN_train(x)) with y == x allowed, and/or (y == NULL) only the affine
  * rows scale/shift (N/samples_per_stat, ld_affine) for a consumer that applies them itself.  Same
- * running-statistics semantics as pf_bn_finalize_f32. */
+ * running-statistics semantics as pf_bn_finalize_jobs_f32. */
 int pf_channel_bn_fused_f32(const float* x, float* y, int64_t N, int64_t C, int64_t S, int samples_per_stat,
                             const float* gamma, const float* beta, float* running_mean, float* running_var,
                             float momentum, float eps, int relu, float* scale, float* shift, int ld_affine,
@@ -729,12 +707,12 @@ int pf_scan_filter_f32(const float* depth, const float* flow_prob, const float* 
  * ATen's convolution_backward / batch_norm backward (MIOpen / CK solvers) in the reference's loss.backward().
  * Everything below sums in a fixed order: gradients are bit-reproducible run to run.
  *
- * Forward finalize that keeps what the backward needs: like pf_bn_finalize_f32, but the result is ONE tensor
+ * Forward finalize that keeps what the backward needs: like pf_bn_finalize_jobs_f32, but the result is ONE tensor
  * rows (4, S, ld_rows) = [scale | shift | mean | invstd], S = G / groups_per_stat; rows[0], rows[1] are the (S, ld)
  * in_scale / in_shift rows the forward kernels take.  The C channels of this call are channels [ch0, ch0 + C) of
  * gamma / beta / the running statistics and land in columns [col_out, col_out + C) of every row (EdgeConv's
  * BatchNorm covers [central | difference] halves with separate statistics, reference networks.py:33-36).  Running
- * statistics updated as by pf_bn_finalize_f32. */
+ * statistics updated as by pf_bn_finalize_jobs_f32. */
 int pf_bn_train_rows_f32(const double* partials, int T, int pcols, int col0, int C, double count, double unbias_n,
                          const float* gamma, const float* beta, float* running_mean, float* running_var,
                          float momentum, float eps, int G, int groups_per_stat, float* rows, int ld_rows, int col_out,
@@ -745,14 +723,12 @@ int pf_bn_train_rows_f32(const double* partials, int T, int pcols, int col0, int
  *            g' = [y * scale + shift > 0] * g when relu != 0, else g;  xhat = (y - mean) * invstd
  *   coeffs : partials (G, T, pcols, 2) -> coef (2, S, C) = [scale * dbeta_s / count | scale * invstd * dgamma_s / count]
  *            and dgamma[c] / dbeta[c] = sum over the S statistic groups (accumulate != 0: added to what is there)
- *   apply  : dy = scale * g' - coef0 - coef1 * (y - mean)           (dy may alias g) */
+ *   apply  : dy = scale * g' - coef0 - coef1 * (y - mean)           (dy may alias g; the two entry points below) */
 int pf_bn_bwd_reduce_f32(const float* g, const float* y, const float* rows, int64_t N, int64_t C, int64_t S,
                          int samples_per_stat, int relu, double* partials, void* stream);
 int pf_bn_bwd_coeffs_f32(const double* partials, int T, int pcols, int col0, int C, double count, int G,
                          int groups_per_stat, const float* rows, float* coef, float* dgamma, float* dbeta,
                          int accumulate, void* stream);
-int pf_bn_bwd_apply_f32(const float* g, const float* y, const float* rows, const float* coef, float* dy, int64_t N,
-                        int64_t C, int64_t S, int samples_per_stat, int relu, void* stream);
 /* coeffs + apply in one launch (the planar path of the training step): every block re-adds its statistic group's
  * partial rows (pf_norm_blocks(S) * samples_per_stat of them, the same order and bits as pf_bn_bwd_coeffs_f32), block
  * (0, c, 0) writes dgamma[c] / dbeta[c] (NULL: not wanted).  count = samples_per_stat * S. */

@@ -9,7 +9,7 @@ import os
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# (PF_LIB_PATH: tools only -- the ablation builds of tools/experiments/build_dbg_variants.sh; the product loads the in-tree library)
+# (PF_LIB_PATH: tools only -- A/B runs against another build of the library; the product loads the in-tree one)
 LIB_PATH = os.environ.get("PF_LIB_PATH") or os.path.join(_HERE, "libpointflow_hip.so")
 
 _vp, _i, _i64, _f, _d = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double
@@ -90,16 +90,12 @@ PROTOTYPES = {
                                   _i64, _i64, _i64, _i, _d, _vp], _i),
     "pf_channel_bn_fused_f32": ([_vp, _vp, _i64, _i64, _i64, _i, _vp, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _i, _vp], _i),
     "pf_edge_stats_f32": ([_vp, _i64, _i, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp], _i),
-    "pf_edge_backward_reduce_f32": ([_vp, _i64, _i, _vp, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp], _i),
-    "pf_edge_backward_apply_f32": ([_vp, _i64, _i, _vp, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i,
-                                    _vp, _vp, _vp, _vp], _i),
     "pf_edge_backward_sums_f32": ([_vp, _i64, _i, _vp, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp,
                                    _i64, _i, _vp], _i),
     "pf_edge_backward_finish_f32": ([_vp, _i64, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i,
                                      _vp, _vp, _vp, _i, _vp], _i),
     "pf_knn_inverse_workspace": ([_i, _i, _i], _i64),
     "pf_knn_inverse": ([_vp, _i, _i, _i, _vp, _vp, _vp, _i64, _vp], _i),
-    "pf_bn_finalize_f32": ([_vp, _i, _i, _i, _i, _d, _d, _vp, _vp, _vp, _vp, _f, _f, _i, _i, _vp, _vp, _i, _vp], _i),
     "pf_bn_finalize_jobs_f32": ([ctypes.POINTER(BnJob), _i, _vp], _i),
     "pf_edge_apply_f32": ([_vp, _i64, _i, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _i64, _vp, _i, _i, _i, _vp], _i),
     "pf_flow_head_f32": ([_vp, _i64, _vp, _vp, _i, ctypes.POINTER(BnJob), _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp,
@@ -147,7 +143,6 @@ PROTOTYPES = {
     "pf_bn_bwd_plane_f32": ([_vp, _vp, _vp, _i64, _i64, _i64, _i, _vp, _vp, _vp, _i, _vp], _i),
     "pf_edge_backward_coeffs_f32": ([_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp], _i),
     "pf_bn_bwd_coeffs_f32": ([_vp, _i, _i, _i, _i, _d, _i, _i, _vp, _vp, _vp, _vp, _i, _vp], _i),
-    "pf_bn_bwd_apply_f32": ([_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _vp], _i),
     "pf_rows_bn_blocks": ([_i, _i], _i),
     "pf_rows_bn_bwd_reduce_f32": ([_vp, _i64, _vp, _i64, _vp, _i, _i, _i, _i, _i, _vp, _vp], _i),
     "pf_rows_bn_bwd_apply_f32": ([_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp], _i),

@@ -117,11 +117,7 @@ struct PatchStager {
       for (int r = 0; r < NIT; ++r) {
         const float* src = xb + (goff[r] + origin);
 #pragma unroll
-#ifdef PF_DBG_NOLOAD
-        for (int j = 0; j < 4; ++j) rx[r][j] = (float)(threadIdx.x + j) + (float)(src - xb) * 1e-9f;
-#else
         for (int j = 0; j < 4; ++j) rx[r][j] = (CIN % 4 == 0 || j < CIN) ? src[j * plane_i] : 0.0f;
-#endif
       }
       return;
     }
@@ -134,11 +130,7 @@ struct PatchStager {
       okmask |= (ok ? 1u : 0u) << r;
       const float* src = xb + (ok ? goff[r] + origin : 4 * q * plane_i);
 #pragma unroll
-#ifdef PF_DBG_NOLOAD
-      for (int j = 0; j < 4; ++j) rx[r][j] = (float)(threadIdx.x + j) + (float)(src - xb) * 1e-9f;
-#else
       for (int j = 0; j < 4; ++j) rx[r][j] = (CIN % 4 == 0 || j < CIN) ? src[j * plane_i] : 0.0f;
-#endif
     }
   }
 
@@ -300,7 +292,7 @@ __global__ __launch_bounds__(256) void conv2d_wide_kernel(const float* __restric
   const int m = lane & 31, h = lane >> 5;
   const int wm = wave / C::NWN, wn = wave % C::NWN;
   unsigned xb_, xn_;
-  pf_xcd_xy<PF_XCD_TOWER>(xb_, xn_);                  // XCD x owns a band of tile rows, not every eighth tile (pf_common.h)
+  pf_xcd_xy(xb_, xn_);                  // XCD x owns a band of tile rows, not every eighth tile (pf_common.h)
   const int n = (int)xn_, bx = (int)xb_;
   const int tw = bx % g.tiles_w, th = bx / g.tiles_w;
   const int oh0 = th * C::TH, ow0 = tw * C::TW;
@@ -438,7 +430,7 @@ __global__ __launch_bounds__(256) void conv2d_wide16_kernel(const float* __restr
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const int li = lane & 15, kq = lane >> 4;
   unsigned xb_, xn_;
-  pf_xcd_xy<PF_XCD_TOWER>(xb_, xn_);
+  pf_xcd_xy(xb_, xn_);
   const int n = (int)xn_, bx = (int)xb_;
   const int plane_i = g.Hi * g.Wi;
   const int set = wide_set(g, n);
@@ -547,11 +539,7 @@ __global__ __launch_bounds__(256) void conv2d_wide16_kernel(const float* __restr
 #pragma unroll
       for (int j = 0; j < CPL; ++j)
 #pragma unroll
-#ifdef PF_DBG_NOMFMA
-        for (int r = 0; r < NR; ++r) acc[r][(j + t) & 3] += a[r].v[j] * b.v[j];
-#else
         for (int r = 0; r < NR; ++r) acc[r] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[r].v[j], b.v[j], acc[r], 0, 0, 0);
-#endif
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int r = 0; r < NR; ++r) a[r] = an[r];
@@ -566,9 +554,6 @@ __global__ __launch_bounds__(256) void conv2d_wide16_kernel(const float* __restr
       if (col_ok) {
 #pragma unroll
         for (int r = 0; r < NR; ++r) {
-#ifdef PF_DBG_NOSTORE
-          if (acc[r][0] == 123.456f)
-#endif
           *reinterpret_cast<f32x4*>(dst + (PAIR ? 2 * r : r) * g.Wo) = acc[r];
 #pragma unroll
           for (int e = 0; e < 4; ++e) {

@@ -26,7 +26,7 @@
 //     is reused for the TD depth slices.  Exact float32: an fmaf chain over (channel group, tap, channel).
 //   * epilogue: accumulators go through a per-wave LDS transpose so that each channel's 16 voxels leave as
 //     one 64-byte segment, and per-channel sum / sum-of-squares are folded into float64 block partials
-//     (the (N, T, C, 2) layout pf_bn_finalize_f32 / pf_channel_bn_apply_f32 consume).
+//     (the (N, T, C, 2) layout pf_bn_finalize_jobs_f32 / pf_channel_bn_apply_f32 consume).
 // Bound: fp32 MFMA (2*27*C_in*C_out flop per voxel vs 4*(C_in + C_out) bytes).
 #include <stdlib.h>
 
@@ -89,9 +89,7 @@ __global__ __launch_bounds__(256, MINW) void conv3d_k3_kernel(const float* __res
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const int li = lane & 15, lk = lane >> 4;
-  unsigned xb_, xn_;
-  pf_xcd_xy<PF_XCD_CONV3D>(xb_, xn_);                 // XCD x owns a contiguous run of each pass's items (pf_common.h)
-  const int n = (int)xn_, bx = (int)xb_;
+  const int n = (int)blockIdx.y, bx = (int)blockIdx.x;
   const int plane_i = g.Hi * g.Wi, vol_i = plane_i * g.Di;       // Cin * vol_i < 2^31 (checked on the host)
   const int64_t plane_o = (int64_t)g.Ho * g.Wo, vol_o = plane_o * g.Do;
   const float* xb = x + (int64_t)n * g.Cin * vol_i;

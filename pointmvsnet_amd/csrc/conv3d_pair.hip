@@ -70,9 +70,7 @@ __global__ __launch_bounds__(256, MINW) void conv3d_k3_pair_kernel(const float* 
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const int li = lane & 15, lk = lane >> 4;
-  unsigned xb_, xn_;
-  pf_xcd_xy<PF_XCD_CONV3D>(xb_, xn_);                 // XCD x owns a contiguous run of each pass's items (pf_common.h)
-  const int n = (int)xn_, bx = (int)xb_;
+  const int n = (int)blockIdx.y, bx = (int)blockIdx.x;
   const int plane_i = g.H * g.W, vol = plane_i * g.D;            // Cin * vol < 2^31 (checked on the host)
   const float* xb = x + (int64_t)n * g.Cin * vol;
   float* yb = y + (int64_t)n * g.Cout * vol;

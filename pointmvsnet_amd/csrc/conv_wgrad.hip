@@ -36,8 +36,6 @@
 //     bit-reproducible run to run (the library's split-K solvers use float atomics).
 // Bound: fp32 MFMA (2 * taps * Cg * Cx flop per position against 4 * (Cg + Cx) bytes); the 8-channel layers fill half
 // of the 16 MFMA rows.
-#include <stdlib.h>
-
 #include "pf_common.h"
 
 namespace {
@@ -69,7 +67,6 @@ struct WgGeom {
   // point-major rows (taps == 1): Gr (P, ldg), X (P, ldx)
   int point_major;
   int64_t P, ldg, ldx;
-  int dbg;                            // PF_WGRAD_DBG (tools only): 1 = no staging, 2 = no MFMA loop, 4 = no partial store
 };
 
 // NTW: column tiles per wave = ceil(NTILES / 4).  Every wave runs NTW tiles -- one that does not exist reads column 0's
@@ -159,8 +156,7 @@ __device__ __forceinline__ void wgrad_body(const float* __restrict__ Gr, const f
     constexpr int kU = MT == 4 ? 4 : 8, kG = 4, kUR = 4;
     const int grows = min(MT * 16, g.Cg - cg0);          // rows / channels that exist: the rest of the LDS tiles is
     const int creal = min(cbtot, g.Cx - ci0);            // never stored from (their products are not written)
-    if (g.dbg & 1) {
-    } else if (g.point_major) {
+    if (g.point_major) {
       // R * 16 consecutive points; thread = (point, 4 channels): coalesced 16-byte row pieces, transposed into LDS
       const int PT = R * 16;
       const int64_t p0 = (int64_t)tile * PT;
@@ -372,7 +368,7 @@ __device__ __forceinline__ void wgrad_body(const float* __restrict__ Gr, const f
     }
     __syncthreads();
 
-    for (int r = 0; r < ((g.dbg & 2) ? 0 : R); ++r) {
+    for (int r = 0; r < R; ++r) {
       const int d = r >> g.lgTH, h = r & (g.TH - 1);
       float a[MT][4];
 #pragma unroll
@@ -407,7 +403,7 @@ __device__ __forceinline__ void wgrad_body(const float* __restrict__ Gr, const f
     const int cil = li & (g.CBP - 1), tl = li >> g.lgCBP;
     const int tap = tg * g.TPT + tl;
     const int ci = ci0 + sub * g.CBP + cil;
-    if (tap >= g.T || ci >= g.Cx || (g.dbg & 4)) continue;
+    if (tap >= g.T || ci >= g.Cx) continue;
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
 #pragma unroll
@@ -606,11 +602,6 @@ WgPlan make_plan_mt(int64_t N, int64_t Cg, int64_t Cx, int64_t Do, int64_t Ho, i
   g.x_sps = 1;
   g.x_pps = 1;
   g.point_major = rows ? 1 : 0;
-  static const int dbg = []() {
-    const char* e = getenv("PF_WGRAD_DBG");
-    return e == nullptr ? 0 : atoi(e);
-  }();
-  g.dbg = dbg;
   g.P = P;
   g.ldg = g.ldx = 0;
   g.CBP = Cx >= 16 ? 16 : (Cx > 4 ? 8 : 4);
@@ -625,17 +616,9 @@ WgPlan make_plan_mt(int64_t N, int64_t Cg, int64_t Cx, int64_t Do, int64_t Ho, i
   // 35 -> 30, profiles/r06j_wgrad_plans.md), then 2 x 4 x 16, 1 x 8 x 16, 1 x 4 x 16; 2-D layers try 1 x 16 x 16 first
   // when it fits the soft LDS budget: twice the matrix work between two barriers of a latency-bound loop
   const int cand[5][2] = {{1, 16}, {2, 4}, {1, 8}, {1, 4}, {4, 4}};
-  static const bool big_tile = []() {
-    const char* e = getenv("PF_WGRAD_BIG_TILE");
-    return e == nullptr || e[0] != '0';
-  }();
-  static const bool big_rows = []() {
-    const char* e = getenv("PF_WGRAD_BIG_ROWS");
-    return e == nullptr || e[0] != '0';
-  }();
   int seq[5], nseq = 0;
   if (rows) {
-    if (big_rows) seq[nseq++] = 2;                             // 128 points per tile (E1, mlp3: +0.3 % on the step)
+    seq[nseq++] = 2;                             // 128 points per tile (E1, mlp3: +0.3 % on the step)
     seq[nseq++] = 3;
   } else if (first_tile == 2) {
     seq[nseq++] = 3;
@@ -645,7 +628,7 @@ WgPlan make_plan_mt(int64_t N, int64_t Cg, int64_t Cx, int64_t Do, int64_t Ho, i
     seq[nseq++] = 2;
     seq[nseq++] = 3;
   } else {
-    if (big_tile && Ho >= 16) seq[nseq++] = 0;
+    if (Ho >= 16) seq[nseq++] = 0;
     seq[nseq++] = 2;
     seq[nseq++] = 3;
   }
@@ -728,7 +711,7 @@ WgPlan make_plan(int64_t N, int64_t Cg, int64_t Cx, int64_t Do, int64_t Ho, int6
   // Rows of Gr per block.  Point-major rows (one tap): as many as there are, up to 64 -- the operands are re-read per
   // row tile.  Planar layers: 16 (32 for the 64-row stride-1 layers): a block's partial dW is rows x channels x taps
   // floats per position slice, and with ~480 resident blocks the slices of the 25-tap and 32-row layers wrote and re-read
-  // 18-25 MB -- 10-25 us of their 40-67 us (PF_WGRAD_DBG=4); fewer rows per block = more row blocks = fewer slices
+  // 18-25 MB -- 10-25 us of their 40-67 us (profiles/r06g_wgrad_ablation.log); fewer rows per block = more row blocks = fewer slices
   // (tower 16->32 / 32->64 5x5: 67 -> 55 us, 32->32: 41 -> 36, conv2_1: 36 -> 26; 64->64 3x3 is best at 32 rows: 40).
   int MT = Cg <= 16 ? 1 : (Cg <= 32 ? 2 : 4);
   if (!rows) MT = (Cg >= 64 && stride == 1) ? 2 : 1;

@@ -26,8 +26,6 @@
 //
 // Algorithmic HBM bytes per point: EdgeConv(C_in->C_out, out C'):
 // 4*C_in + 8*16 + 16*4*C_out + 4*C'.
-#include <stdlib.h>
-
 #include "pf_common.h"
 #include "pf_bn_resolve.h"
 
@@ -675,16 +673,14 @@ __global__ __launch_bounds__(256) void edge_apply_kernel(const float* __restrict
 // dl = -sum_j dd_j,  de[idx_j] += dd_j.  The central half of EdgeConv (k identical copies of l through the
 // same BatchNorm) reduces to  dl += a_c * (g_c - dbeta_c/N - xhat_c * dgamma_c/N),  g_c = [u_c > 0] * G_c.
 //
-//   pass 1 (edge_bwd_reduce)  per-block float64 partial sums of (g, g*xhat) per channel -> dbeta, dgamma
-//   pass 2 (edge_bwd_apply)   dl rows (plain stores) and, SCATTER, de rows by float atomics like the reference
-//   pass 3 (edge_bwd_inverse) de rows WITHOUT atomics: point m sums dd over the pairs (n, j) that gathered it, in
-//                             ascending pair order, from the inverted index tensor (knn_inverse.hip) -- the same
-//                             dd expression as pass 2, so dl and de are bit-reproducible from run to run
-// Round 6, the default with inverted lists: TWO walks.  dl = -sum_j dd_j is linear in (dbeta, dgamma):
-//   dl = -a * ((sum_j g_j - k * dbeta/M) - (dgamma/M) * sum_j xhat_j),
-// so pass 1 (edge_bwd_reduce<.., SUMS>) leaves each point's (sum_j g_j | sum_j xhat_j) in its dLE row and pass 3
-// (edge_bwd_inverse<.., FINISH>) turns them into dl while it gathers de: pass 2's walk over the forward lists (186 us of
-// the config-4 step) is gone; dl differs from the three-pass form in float32 rounding only.
+// Two passes, and de is gathered, never scattered, so dl and de are bit-reproducible from run to run.  What makes two
+// enough: dl = -sum_j dd_j is linear in (dbeta, dgamma),
+//   dl = -a * ((sum_j g_j - k * dbeta/M) - (dgamma/M) * sum_j xhat_j).
+//   pass 1 (edge_bwd_reduce)   walks the forward lists: per-block float64 partial sums of (g, g*xhat) per channel
+//                              -> dbeta, dgamma; each point's own (sum_j g_j | sum_j xhat_j) goes to its dLE row
+//   pass 2 (edge_bwd_inverse)  walks the inverted lists (knn_inverse.hip): point m sums dd over the pairs (n, j) that
+//                              gathered it, in ascending pair order -> de; the row's sums become dl by the line above
+// (profiles/r06s_edge_backward_two_walks.md: against a separate dl pass over the forward lists.)
 // The two GEMMs that follow (dX = [dl|de] W, dW = [dl|de]^T X) are pointwise_gemm / conv_wgrad launches.
 // ------------------------------------------------------------------------------------------------
 struct EdgeBwdAffine {
@@ -692,12 +688,12 @@ struct EdgeBwdAffine {
   const float* shift;
   const float* mean;
   const float* invstd;
-  const float* c1;         // pass 2: dbeta / M  (central columns: / N)
+  const float* c1;         // pass 2: dbeta / M  (central columns: / N); null in pass 1
   const float* c2;         // pass 2: dgamma / M
   int ld, groups_per_stat, concat;
 };
 
-template <int C, int K, bool SUMS>
+template <int C, int K>
 __global__ __launch_bounds__(256) void edge_bwd_reduce_kernel(const float* __restrict__ LE, int64_t ldle,
                                                               const int64_t* __restrict__ idx, int k, int Ng,
                                                               const float* __restrict__ Gy, int64_t ldg,
@@ -738,7 +734,7 @@ __global__ __launch_bounds__(256) void edge_bwd_reduce_kernel(const float* __res
       const int64_t row = gbase + n;
       const float4 l = ld4(LE + row * ldle + 4 * q);
       float4 gy = ld4(Gy + row * ldg + doff + 4 * q);
-      if (SUMS && gacc != nullptr) {     // a second gradient meets this one here (the next layer's data gradient):
+      if (gacc != nullptr) {     // a second gradient meets this one here (the next layer's data gradient):
         float* ga = gacc + row * lda + doff + 4 * q;           // the sum replaces it, the later passes read gacc
         const float4 h = ld4(ga);
         gy = make_float4(gy.x + h.x, gy.y + h.y, gy.z + h.z, gy.w + h.w);
@@ -759,7 +755,7 @@ __global__ __launch_bounds__(256) void edge_bwd_reduce_kernel(const float* __res
           const float gg = u > 0.0f ? gd[c] : 0.0f;
           sg[c] += gg;
           sx[c] += gg * ((d - mv[c]) * iv[c]);
-          if (SUMS) sd[c] += d;
+          sd[c] += d;
         }
       };
       if constexpr (K > 0) {
@@ -782,15 +778,14 @@ __global__ __launch_bounds__(256) void edge_bwd_reduce_kernel(const float* __res
         acc[c] += (double)sg[c];
         acc[4 + c] += (double)sx[c];
       }
-      if (SUMS) {   // the point's own sums over its k pairs: [sum g | sum xhat] in the row the finish pass turns into [dl | de]
-        float* o = sums + row * ldle + 4 * q;
-        *reinterpret_cast<float4*>(o) = make_float4(sg[0], sg[1], sg[2], sg[3]);
-        *reinterpret_cast<float4*>(o + C) = make_float4((sd[0] - kf * mv[0]) * iv[0], (sd[1] - kf * mv[1]) * iv[1],
-                                                        (sd[2] - kf * mv[2]) * iv[2], (sd[3] - kf * mv[3]) * iv[3]);
-      }
+      // the point's own sums over its k pairs: [sum g | sum xhat] in the row the finish pass turns into [dl | de]
+      float* o = sums + row * ldle + 4 * q;
+      *reinterpret_cast<float4*>(o) = make_float4(sg[0], sg[1], sg[2], sg[3]);
+      *reinterpret_cast<float4*>(o + C) = make_float4((sd[0] - kf * mv[0]) * iv[0], (sd[1] - kf * mv[1]) * iv[1],
+                                                      (sd[2] - kf * mv[2]) * iv[2], (sd[3] - kf * mv[3]) * iv[3]);
       if (A.concat) {
         float4 gc4 = ld4(Gy + row * ldg + 4 * q);
-        if (SUMS && gacc != nullptr) {
+        if (gacc != nullptr) {
           float* ga = gacc + row * lda + 4 * q;
           const float4 h = ld4(ga);
           gc4 = make_float4(gc4.x + h.x, gc4.y + h.y, gc4.z + h.z, gc4.w + h.w);
@@ -827,97 +822,12 @@ __global__ __launch_bounds__(256) void edge_bwd_reduce_kernel(const float* __res
   }
 }
 
-template <int C, int K, bool SCATTER>
-__global__ __launch_bounds__(256) void edge_bwd_apply_kernel(const float* __restrict__ LE, int64_t ldle,
-                                                             const int64_t* __restrict__ idx, int k, int Ng,
-                                                             const float* __restrict__ Gy, int64_t ldg,
-                                                             EdgeBwdAffine A, float* __restrict__ dLE, int T) {
-  constexpr int Q = C / 4;
-  constexpr int PPB = 256 / Q;
-  const int tid = threadIdx.x;
-  const int q = tid % Q, pl = tid / Q;
-  const int g = blockIdx.y, tb = blockIdx.x;
-  const int tiles = (Ng + TILE - 1) / TILE;
-  const int64_t gbase = (int64_t)g * Ng;
-  const int64_t so = (int64_t)(g / A.groups_per_stat) * A.ld;
-  const int doff = A.concat ? C : 0;
-  const float4 a = ld4(A.scale + so + doff + 4 * q), b = ld4(A.shift + so + doff + 4 * q);
-  const float4 mu = ld4(A.mean + so + doff + 4 * q), is = ld4(A.invstd + so + doff + 4 * q);
-  const float4 k1 = ld4(A.c1 + so + doff + 4 * q), k2 = ld4(A.c2 + so + doff + 4 * q);
-  const float av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {b.x, b.y, b.z, b.w};
-  const float mv[4] = {mu.x, mu.y, mu.z, mu.w}, iv[4] = {is.x, is.y, is.z, is.w};
-  const float c1v[4] = {k1.x, k1.y, k1.z, k1.w}, c2v[4] = {k2.x, k2.y, k2.z, k2.w};
-  const float kf = (float)k;
-  for (int tile = tb; tile < tiles; tile += T) {
-    const int n0 = tile * TILE;
-    for (int p = pl; p < TILE; p += PPB) {
-      const int n = n0 + p;
-      if (n >= Ng) break;
-      const int64_t row = gbase + n;
-      const float4 l = ld4(LE + row * ldle + 4 * q);
-      const float4 gy = ld4(Gy + row * ldg + doff + 4 * q);
-      const float gd[4] = {gy.x / kf, gy.y / kf, gy.z / kf, gy.w / kf};
-      const float lv[4] = {l.x, l.y, l.z, l.w};
-      float dl[4] = {0, 0, 0, 0};
-      const int64_t* ip = idx + row * k;
-      auto pair = [&](const float4& e, int64_t i) {
-        const float ev[4] = {e.x, e.y, e.z, e.w};
-        float* de = dLE + (gbase + i) * ldle + C + 4 * q;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const float d = ev[c] - lv[c];
-          const float u = fmaf(d, av[c], bv[c]);
-          const float gg = u > 0.0f ? gd[c] : 0.0f;
-          const float dd = av[c] * ((gg - c1v[c]) - ((d - mv[c]) * iv[c]) * c2v[c]);
-          dl[c] -= dd;
-          if (SCATTER) unsafeAtomicAdd(de + c, dd);
-        }
-      };
-      if constexpr (K > 0) {
-        float4 e[K > 0 ? K : 1];
-        bool bad = false;
-        gather_rows<C, (K > 0 ? K : 2)>(LE, ldle, ip, gbase, Ng, q, e, bad);
-#pragma unroll
-        for (int j = 0; j < K; ++j) {
-          int64_t i = ip[j];
-          i = i < 0 ? 0 : (i >= Ng ? Ng - 1 : i);
-          pair(e[j], i);
-        }
-      } else {
-        for (int j = 0; j < k; ++j) {
-          int64_t i = ip[j];
-          i = i < 0 ? 0 : (i >= Ng ? Ng - 1 : i);
-          pair(ld4(LE + (gbase + i) * ldle + C + 4 * q), i);
-        }
-      }
-      if (A.concat) {
-        const float4 gc4 = ld4(Gy + row * ldg + 4 * q);
-        const float gcv[4] = {gc4.x, gc4.y, gc4.z, gc4.w};
-        const float4 ac = ld4(A.scale + so + 4 * q), bc = ld4(A.shift + so + 4 * q);
-        const float4 muc = ld4(A.mean + so + 4 * q), isc = ld4(A.invstd + so + 4 * q);
-        const float4 k1c = ld4(A.c1 + so + 4 * q), k2c = ld4(A.c2 + so + 4 * q);
-        const float acv[4] = {ac.x, ac.y, ac.z, ac.w}, bcv[4] = {bc.x, bc.y, bc.z, bc.w};
-        const float mcv[4] = {muc.x, muc.y, muc.z, muc.w}, icv[4] = {isc.x, isc.y, isc.z, isc.w};
-        const float c1c[4] = {k1c.x, k1c.y, k1c.z, k1c.w}, c2c[4] = {k2c.x, k2c.y, k2c.z, k2c.w};
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const float u = fmaf(lv[c], acv[c], bcv[c]);
-          const float gg = u > 0.0f ? gcv[c] : 0.0f;
-          dl[c] += acv[c] * ((gg - c1c[c]) - ((lv[c] - mcv[c]) * icv[c]) * c2c[c]);
-        }
-      }
-      *reinterpret_cast<float4*>(dLE + row * ldle + 4 * q) = make_float4(dl[0], dl[1], dl[2], dl[3]);
-    }
-  }
-}
-
-template <int C, bool FINISH>
+template <int C>
 __global__ __launch_bounds__(256, 3) void edge_bwd_inverse_kernel(const float* __restrict__ LE, int64_t ldle, int k, int Ng,
                                                                const float* __restrict__ Gy, int64_t ldg,
                                                                EdgeBwdAffine A, const uint32_t* __restrict__ order,
                                                                const uint32_t* __restrict__ start,
-                                                               float* __restrict__ dLE, int64_t rows, int dbg,
-                                                               int band) {
+                                                               float* __restrict__ dLE, int64_t rows, int band) {
   constexpr int Q = C / 4;
   constexpr int PPB = 256 / Q;
   const int tid = threadIdx.x;
@@ -944,14 +854,12 @@ __global__ __launch_bounds__(256, 3) void edge_bwd_inverse_kernel(const float* _
     const float ev[4] = {e.x, e.y, e.z, e.w};
     const uint32_t t0 = start[row], t1 = live ? start[row + 1] : t0;
     float de[4] = {0, 0, 0, 0};
-    float4 sg4 = {0, 0, 0, 0}, sx4 = {0, 0, 0, 0}, l4 = {0, 0, 0, 0}, gc4 = {0, 0, 0, 0};
-    if (FINISH && !(dbg & 1)) {       // issued before the list walk: their latency hides behind it
-      sg4 = ld4(dLE + row * ldle + 4 * q);
-      sx4 = ld4(dLE + row * ldle + C + 4 * q);
-      if (A.concat && !(dbg & 4)) {
-        l4 = ld4(LE + row * ldle + 4 * q);
-        gc4 = ld4(Gy + row * ldg + 4 * q);
-      }
+    // the row's own sums (pass 1), issued before the list walk: their latency hides behind it
+    const float4 sg4 = ld4(dLE + row * ldle + 4 * q), sx4 = ld4(dLE + row * ldle + C + 4 * q);
+    float4 l4 = {0, 0, 0, 0}, gc4 = {0, 0, 0, 0};
+    if (A.concat) {
+      l4 = ld4(LE + row * ldle + 4 * q);
+      gc4 = ld4(Gy + row * ldg + 4 * q);
     }
     auto pair_term = [&](const float4& lq, const float4& gq, const float* evv, float* acc) {
       const float lv[4] = {lq.x, lq.y, lq.z, lq.w};
@@ -1043,30 +951,28 @@ __global__ __launch_bounds__(256, 3) void edge_bwd_inverse_kernel(const float* _
         }
       }
     }
-    if (FINISH) {
-      // dl from the row's own sums (edge_bwd_reduce_kernel<.., true>): dl = -sum_j dd_j is linear in (c1, c2), so
-      //   dl = -a * ((sum_j g_j - k * c1) - c2 * sum_j xhat_j)  -- no second walk over the neighbour rows.
-      const float sgv[4] = {sg4.x, sg4.y, sg4.z, sg4.w}, sxv[4] = {sx4.x, sx4.y, sx4.z, sx4.w};
-      float dl[4];
+    // dl from the row's own sums (edge_bwd_reduce_kernel): dl = -sum_j dd_j is linear in (c1, c2), so
+    //   dl = -a * ((sum_j g_j - k * c1) - c2 * sum_j xhat_j)  -- no second walk over the neighbour rows.
+    const float sgv[4] = {sg4.x, sg4.y, sg4.z, sg4.w}, sxv[4] = {sx4.x, sx4.y, sx4.z, sx4.w};
+    float dl[4];
 #pragma unroll
-      for (int c = 0; c < 4; ++c) dl[c] = -av[c] * ((sgv[c] - kf * c1v[c]) - c2v[c] * sxv[c]);
-      if (A.concat && !(dbg & 4)) {
-        const int64_t sc = (int64_t)(g / A.groups_per_stat) * A.ld + 4 * q;
-        const float4 ac = ld4(A.scale + sc), bc = ld4(A.shift + sc), muc = ld4(A.mean + sc), isc = ld4(A.invstd + sc);
-        const float4 k1c = ld4(A.c1 + sc), k2c = ld4(A.c2 + sc);
-        const float lv[4] = {l4.x, l4.y, l4.z, l4.w}, gcv[4] = {gc4.x, gc4.y, gc4.z, gc4.w};
-        const float acv[4] = {ac.x, ac.y, ac.z, ac.w}, bcv[4] = {bc.x, bc.y, bc.z, bc.w};
-        const float mcv[4] = {muc.x, muc.y, muc.z, muc.w}, icv[4] = {isc.x, isc.y, isc.z, isc.w};
-        const float c1c[4] = {k1c.x, k1c.y, k1c.z, k1c.w}, c2c[4] = {k2c.x, k2c.y, k2c.z, k2c.w};
+    for (int c = 0; c < 4; ++c) dl[c] = -av[c] * ((sgv[c] - kf * c1v[c]) - c2v[c] * sxv[c]);
+    if (A.concat) {
+      const int64_t sc = (int64_t)(g / A.groups_per_stat) * A.ld + 4 * q;
+      const float4 ac = ld4(A.scale + sc), bc = ld4(A.shift + sc), muc = ld4(A.mean + sc), isc = ld4(A.invstd + sc);
+      const float4 k1c = ld4(A.c1 + sc), k2c = ld4(A.c2 + sc);
+      const float lv[4] = {l4.x, l4.y, l4.z, l4.w}, gcv[4] = {gc4.x, gc4.y, gc4.z, gc4.w};
+      const float acv[4] = {ac.x, ac.y, ac.z, ac.w}, bcv[4] = {bc.x, bc.y, bc.z, bc.w};
+      const float mcv[4] = {muc.x, muc.y, muc.z, muc.w}, icv[4] = {isc.x, isc.y, isc.z, isc.w};
+      const float c1c[4] = {k1c.x, k1c.y, k1c.z, k1c.w}, c2c[4] = {k2c.x, k2c.y, k2c.z, k2c.w};
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const float u = fmaf(lv[c], acv[c], bcv[c]);
-          const float gg = u > 0.0f ? gcv[c] : 0.0f;
-          dl[c] += acv[c] * ((gg - c1c[c]) - ((lv[c] - mcv[c]) * icv[c]) * c2c[c]);
-        }
+      for (int c = 0; c < 4; ++c) {
+        const float u = fmaf(lv[c], acv[c], bcv[c]);
+        const float gg = u > 0.0f ? gcv[c] : 0.0f;
+        dl[c] += acv[c] * ((gg - c1c[c]) - ((lv[c] - mcv[c]) * icv[c]) * c2c[c]);
       }
-      if (!(dbg & 2) && live) *reinterpret_cast<float4*>(dLE + row * ldle + 4 * q) = make_float4(dl[0], dl[1], dl[2], dl[3]);
     }
+    if (live) *reinterpret_cast<float4*>(dLE + row * ldle + 4 * q) = make_float4(dl[0], dl[1], dl[2], dl[3]);
     if (live) *reinterpret_cast<float4*>(dLE + row * ldle + C + 4 * q) = make_float4(de[0], de[1], de[2], de[3]);
   }
 }
@@ -1435,10 +1341,9 @@ static int check_lattice(const int64_t* idx, const uint8_t* codes, int k, int Ng
 }
 
 // XCD-aware tile order (Lattice::band) where the launch allows it: whole tiles per plane, a multiple of 8 of them, one
-// tile per block.  PF_EDGE_XCD=0 keeps tile = block (tools: the A/B arm).
+// tile per block; 0 otherwise (tile = block).
 static int xcd_band(int64_t plane, int unit, int64_t Ng, int64_t blocks) {      // units of `unit` points per block
-  static const bool on = !(getenv("PF_EDGE_XCD") && atoi(getenv("PF_EDGE_XCD")) == 0);
-  if (!on || plane <= 1 || plane % unit != 0 || (plane / unit) % 8 != 0 || Ng % plane != 0 || blocks != Ng / unit) return 0;
+  if (plane <= 1 || plane % unit != 0 || (plane / unit) % 8 != 0 || Ng % plane != 0 || blocks != Ng / unit) return 0;
   return (int)(plane / unit / 8);
 }
 static void lattice_band(Lattice& lat, int Ng, int T) { lat.band = xcd_band((int64_t)lat.H * lat.W, TILE, Ng, T); }
@@ -1490,33 +1395,6 @@ int pf_bn_finalize_jobs_f32(const pf_bn_job* jobs, int njobs, void* stream) {
   return pf_launch_status();
 }
 
-int pf_bn_finalize_f32(const double* partials, int T, int pcols, int col0, int C, double count, double unbias_n,
-                       const float* gamma, const float* beta, float* running_mean, float* running_var,
-                       float momentum, float eps, int G, int groups_per_stat, float* scale, float* shift,
-                       int ld_affine, void* stream) {
-  pf_bn_job j;
-  j.partials = partials;
-  j.T = T;
-  j.pcols = pcols;
-  j.col0 = col0;
-  j.C = C;
-  j.count = count;
-  j.unbias_n = unbias_n;
-  j.gamma = gamma;
-  j.beta = beta;
-  j.running_mean = running_mean;
-  j.running_var = running_var;
-  j.momentum = momentum;
-  j.eps = eps;
-  j.G = G;
-  j.groups_per_stat = groups_per_stat;
-  j.scale = scale;
-  j.shift = shift;
-  j.ld_affine = ld_affine;
-  j.rows4 = 0;
-  return pf_bn_finalize_jobs_f32(&j, 1, stream);
-}
-
 int pf_edge_apply_f32(const float* LE, int64_t ldle, int C, const int64_t* idx, int k, int G, int Ng,
                       const float* scale, const float* shift, int ld_affine, int groups_per_stat, int concat,
                       float* Y, int64_t ldy, const uint8_t* codes, int lat_ks, int lat_h, int lat_w, void* stream) {
@@ -1547,14 +1425,15 @@ int pf_edge_apply_f32(const float* LE, int64_t ldle, int C, const int64_t* idx, 
   return pf_launch_status();
 }
 
-extern "C++" {
-static int edge_backward_reduce(const float* LE, int64_t ldle, int C, const int64_t* idx, int k, int G, int Ng,
-                                const float* grad_y, int64_t ldg, const float* scale, const float* shift,
-                                const float* mean, const float* invstd, int ld_affine, int groups_per_stat,
-                                int concat, double* partials, float* sums, float* gacc, int64_t lda, int plane,
-                                void* stream) {
+int pf_edge_backward_sums_f32(const float* LE, int64_t ldle, int C, const int64_t* idx, int k, int G, int Ng,
+                              const float* grad_y, int64_t ldg, const float* scale, const float* shift,
+                              const float* mean, const float* invstd, int ld_affine, int groups_per_stat, int concat,
+                              double* partials, float* grad_le, float* grad_acc, int64_t ld_acc, int plane,
+                              void* stream) {
+  PF_REQUIRE(grad_le != nullptr || G == 0 || Ng == 0);
+  PF_REQUIRE(plane >= 0);
   PF_REQUIRE(G >= 0 && Ng >= 0 && k >= 1 && ldle >= 2 * (int64_t)C && (ldle % 4) == 0 && G <= 65535);
-  PF_REQUIRE(gacc == nullptr || (sums != nullptr && (lda % 4) == 0 && lda >= (concat ? 2 : 1) * (int64_t)C));
+  PF_REQUIRE(grad_acc == nullptr || (grad_le != nullptr && (ld_acc % 4) == 0 && ld_acc >= (concat ? 2 : 1) * (int64_t)C));
   PF_REQUIRE(groups_per_stat >= 1 && (ldg % 4) == 0 && ldg >= (concat ? 2 : 1) * (int64_t)C);
   PF_REQUIRE((ld_affine % 4) == 0 && ld_affine >= (concat ? 2 : 1) * C);
   if (C != 32 && C != 64) return PF_ERR_UNSUPPORTED;
@@ -1567,99 +1446,13 @@ static int edge_backward_reduce(const float* LE, int64_t ldle, int C, const int6
   const int band = xcd_band(plane, TILE, Ng, T);
   dim3 grid((unsigned)T, (unsigned)G);
   hipStream_t s = (hipStream_t)stream;
-#define PF_EBR(CV, KV, SV) hipLaunchKernelGGL((edge_bwd_reduce_kernel<CV, KV, SV>), grid, dim3(256), 0, s, LE, ldle, idx, k, Ng, grad_y, ldg, A, partials, T, status, sums, gacc, lda, band)
-  if (sums != nullptr) {
-    if (k == 16) {
-      if (C == 32) PF_EBR(32, 16, true); else PF_EBR(64, 16, true);
-    } else {
-      if (C == 32) PF_EBR(32, 0, true); else PF_EBR(64, 0, true);
-    }
-  } else if (k == 16) {
-    if (C == 32) PF_EBR(32, 16, false); else PF_EBR(64, 16, false);
+#define PF_EBR(CV, KV) hipLaunchKernelGGL((edge_bwd_reduce_kernel<CV, KV>), grid, dim3(256), 0, s, LE, ldle, idx, k, Ng, grad_y, ldg, A, partials, T, status, grad_le, grad_acc, ld_acc, band)
+  if (k == 16) {
+    if (C == 32) PF_EBR(32, 16); else PF_EBR(64, 16);
   } else {
-    if (C == 32) PF_EBR(32, 0, false); else PF_EBR(64, 0, false);
+    if (C == 32) PF_EBR(32, 0); else PF_EBR(64, 0);
   }
 #undef PF_EBR
-  return pf_launch_status();
-}
-}  // extern "C++"
-
-int pf_edge_backward_reduce_f32(const float* LE, int64_t ldle, int C, const int64_t* idx, int k, int G, int Ng,
-                                const float* grad_y, int64_t ldg, const float* scale, const float* shift,
-                                const float* mean, const float* invstd, int ld_affine, int groups_per_stat,
-                                int concat, double* partials, void* stream) {
-  return edge_backward_reduce(LE, ldle, C, idx, k, G, Ng, grad_y, ldg, scale, shift, mean, invstd, ld_affine,
-                              groups_per_stat, concat, partials, nullptr, nullptr, 0, 0, stream);
-}
-
-int pf_edge_backward_sums_f32(const float* LE, int64_t ldle, int C, const int64_t* idx, int k, int G, int Ng,
-                              const float* grad_y, int64_t ldg, const float* scale, const float* shift,
-                              const float* mean, const float* invstd, int ld_affine, int groups_per_stat, int concat,
-                              double* partials, float* grad_le, float* grad_acc, int64_t ld_acc, int plane,
-                              void* stream) {
-  PF_REQUIRE(grad_le != nullptr || G == 0 || Ng == 0);
-  PF_REQUIRE(plane >= 0);
-  return edge_backward_reduce(LE, ldle, C, idx, k, G, Ng, grad_y, ldg, scale, shift, mean, invstd, ld_affine,
-                              groups_per_stat, concat, partials, grad_le, grad_acc, ld_acc, plane, stream);
-}
-
-extern "C++" {
-template <bool FINISH>
-static void edge_backward_inverse_launch(const float* LE, int64_t ldle, int C, int k, int G, int Ng, const float* grad_y,
-                                         int64_t ldg, const EdgeBwdAffine& A, const uint32_t* inv_order,
-                                         const uint32_t* inv_start, float* grad_le, int plane, hipStream_t s) {
-  const int64_t rows = (int64_t)G * Ng;
-  const int ppb = 256 / (C / 4);
-  int64_t blocks = pf_cdiv(rows, ppb);
-  if (blocks > 16384) blocks = 16384;
-  const int band = G == 1 ? xcd_band(plane, ppb, Ng, blocks) : 0;
-  static const int dbg = getenv("PF_EDGE_FINISH_DBG") ? atoi(getenv("PF_EDGE_FINISH_DBG")) : 0;   // tools only: wrong results
-  if (C == 32)
-    hipLaunchKernelGGL((edge_bwd_inverse_kernel<32, FINISH>), dim3((unsigned)blocks), dim3(256), 0, s, LE, ldle, k, Ng,
-                       grad_y, ldg, A, inv_order, inv_start, grad_le, rows, dbg, band);
-  else
-    hipLaunchKernelGGL((edge_bwd_inverse_kernel<64, FINISH>), dim3((unsigned)blocks), dim3(256), 0, s, LE, ldle, k, Ng,
-                       grad_y, ldg, A, inv_order, inv_start, grad_le, rows, dbg, band);
-}
-}  // extern "C++"
-
-int pf_edge_backward_apply_f32(const float* LE, int64_t ldle, int C, const int64_t* idx, int k, int G, int Ng,
-                               const float* grad_y, int64_t ldg, const float* scale, const float* shift,
-                               const float* mean, const float* invstd, const float* c1, const float* c2,
-                               int ld_affine, int groups_per_stat, int concat, float* grad_le,
-                               const uint32_t* inv_order, const uint32_t* inv_start, void* stream) {
-  PF_REQUIRE(G >= 0 && Ng >= 0 && k >= 1 && ldle >= 2 * (int64_t)C && (ldle % 4) == 0 && G <= 65535);
-  PF_REQUIRE((inv_order == nullptr) == (inv_start == nullptr));
-  PF_REQUIRE(groups_per_stat >= 1 && (ldg % 4) == 0 && ldg >= (concat ? 2 : 1) * (int64_t)C);
-  PF_REQUIRE((ld_affine % 4) == 0 && ld_affine >= (concat ? 2 : 1) * C);
-  if (C != 32 && C != 64) return PF_ERR_UNSUPPORTED;
-  if (G == 0 || Ng == 0) return PF_OK;
-  PF_REQUIRE(LE && idx && grad_y && scale && shift && mean && invstd && c1 && c2 && grad_le);
-  hipStream_t s = (hipStream_t)stream;
-  const bool scatter = inv_order == nullptr;
-  if (scatter) {     // the atomics accumulate into de: clear it first (the inverse gather writes every row itself)
-    const int zrc = pf_zero_async(grad_le, sizeof(float) * (size_t)G * Ng * ldle, s);
-    if (zrc != PF_OK) return zrc;
-  }
-  const EdgeBwdAffine A{scale, shift, mean, invstd, c1, c2, ld_affine, groups_per_stat, concat};
-  const int T = pf_stat_blocks(G, Ng);
-  dim3 grid((unsigned)T, (unsigned)G);
-#define PF_EBA(CV, KV, SV) hipLaunchKernelGGL((edge_bwd_apply_kernel<CV, KV, SV>), grid, dim3(256), 0, s, LE, ldle, idx, k, Ng, grad_y, ldg, A, grad_le, T)
-  if (scatter) {
-    if (k == 16) {
-      if (C == 32) PF_EBA(32, 16, true); else PF_EBA(64, 16, true);
-    } else {
-      if (C == 32) PF_EBA(32, 0, true); else PF_EBA(64, 0, true);
-    }
-    return pf_launch_status();
-  }
-  if (k == 16) {
-    if (C == 32) PF_EBA(32, 16, false); else PF_EBA(64, 16, false);
-  } else {
-    if (C == 32) PF_EBA(32, 0, false); else PF_EBA(64, 0, false);
-  }
-#undef PF_EBA
-  edge_backward_inverse_launch<false>(LE, ldle, C, k, G, Ng, grad_y, ldg, A, inv_order, inv_start, grad_le, 0, s);
   return pf_launch_status();
 }
 
@@ -1675,8 +1468,18 @@ int pf_edge_backward_finish_f32(const float* LE, int64_t ldle, int C, int k, int
   if (G == 0 || Ng == 0) return PF_OK;
   PF_REQUIRE(LE && grad_y && scale && shift && mean && invstd && c1 && c2 && grad_le && inv_order && inv_start);
   const EdgeBwdAffine A{scale, shift, mean, invstd, c1, c2, ld_affine, groups_per_stat, concat};
-  edge_backward_inverse_launch<true>(LE, ldle, C, k, G, Ng, grad_y, ldg, A, inv_order, inv_start, grad_le, plane,
-                                     (hipStream_t)stream);
+  const int64_t rows = (int64_t)G * Ng;
+  const int ppb = 256 / (C / 4);
+  int64_t blocks = pf_cdiv(rows, ppb);
+  if (blocks > 16384) blocks = 16384;
+  const int band = G == 1 ? xcd_band(plane, ppb, Ng, blocks) : 0;
+  hipStream_t s = (hipStream_t)stream;
+  if (C == 32)
+    hipLaunchKernelGGL((edge_bwd_inverse_kernel<32>), dim3((unsigned)blocks), dim3(256), 0, s, LE, ldle, k, Ng,
+                       grad_y, ldg, A, inv_order, inv_start, grad_le, rows, band);
+  else
+    hipLaunchKernelGGL((edge_bwd_inverse_kernel<64>), dim3((unsigned)blocks), dim3(256), 0, s, LE, ldle, k, Ng,
+                       grad_y, ldg, A, inv_order, inv_start, grad_le, rows, band);
   return pf_launch_status();
 }
 

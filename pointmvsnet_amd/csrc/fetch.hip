@@ -209,11 +209,7 @@ __global__ __launch_bounds__(256) void frustum_variance_cl_kernel(const float* _
   const int q = threadIdx.x & 15, pl = threadIdx.x >> 4;
   const int64_t b = blockIdx.y;
   const int hw = H * W;
-  // (XCD x owns a band of pixel rows at ALL depths: the depth planes of a pixel sample neighbouring texels -- pf_common.h)
-  unsigned ptile = blockIdx.x;
-  if ((PF_XCD & PF_XCD_FRUSTUM) != 0 && hw % PTS == 0 && (int64_t)gridDim.x * PTS == N && (gridDim.x & 7u) == 0u)
-    ptile = pf_xcd_band(ptile, (unsigned)(hw / PTS));
-  const int64_t n0 = (int64_t)ptile * PTS;
+  const int64_t n0 = (int64_t)blockIdx.x * PTS;
   const float* ki = fr.kinv + b * 9;
   const float* ri = fr.rinv + b * 9;
   const float* tt = fr.t + b * 3;
@@ -426,9 +422,7 @@ __global__ __launch_bounds__(256) void flow_features_hyp_kernel(const float* __r
   const int q = threadIdx.x & (kFeatLanes - 1);
   const int pl = threadIdx.x / kFeatLanes;
   const int tiles_x = (w + kFeatPX - 1) / kFeatPX;
-  // (XCD x owns a band of patch rows: the bilinear footprints of neighbouring patches overlap -- pf_common.h)
-  const unsigned blk = (PF_XCD & PF_XCD_FETCH) ? pf_xcd_chunk(blockIdx.x, gridDim.x) : blockIdx.x;
-  const int bx = (int)blk % tiles_x, by = (int)blk / tiles_x;
+  const int bx = (int)blockIdx.x % tiles_x, by = (int)blockIdx.x / tiles_x;
   const int y_raw = by * kFeatPY + pl / kFeatPX, x_raw = bx * kFeatPX + pl % kFeatPX;
   const bool live = y_raw < h && x_raw < w;
   const int y = live ? y_raw : h - 1, x = live ? x_raw : w - 1;

@@ -3,7 +3,7 @@
 //
 // The library BatchNorm the reference ends up in costs ~26 us per call on MI355X regardless of size
 // (rocprofv3, profiles/r01_*): 70 calls per depth map.  Here: one streaming reduction (float4 loads,
-// float64 block partials in the same (G, T, C, 2) layout pf_bn_finalize_f32 consumes), the shared
+// float64 block partials in the same (G, T, C, 2) layout pf_bn_finalize_jobs_f32 consumes), the shared
 // finalize kernel, and one streaming normalise+ReLU pass in place.  Both passes are HBM-bound:
 // 4*N*C*S bytes read, then read + written.
 #include "pf_common.h"

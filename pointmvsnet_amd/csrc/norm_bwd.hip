@@ -208,44 +208,6 @@ __global__ __launch_bounds__(256) void bn_bwd_coeffs_kernel(const double* __rest
   }
 }
 
-// grid = (blocks, C, N): dy = scale * g' - k1 - k2 * (y - mean)
-__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restrict__ g, const float* __restrict__ y,
-                                                           const float* __restrict__ rows,
-                                                           const float* __restrict__ coef, float* __restrict__ dy,
-                                                           int C, int64_t S, int sps, int relu) {
-  const int c = blockIdx.y, n = blockIdx.z;
-  const int s = n / sps;
-  const int64_t SC = (int64_t)(gridDim.z / sps) * C;
-  const float* r = rows + (int64_t)s * C + c;
-  const float sc = r[0], sh = r[SC], mean = r[2 * SC];
-  const float k1 = coef[(int64_t)s * C + c], k2 = coef[SC + (int64_t)s * C + c];
-  const float* pg = g + ((int64_t)n * C + c) * S;
-  const float* py = y + ((int64_t)n * C + c) * S;
-  float* po = dy + ((int64_t)n * C + c) * S;
-  auto one = [&](float gv, float yv) {
-    const float m = masked(gv, yv, sc, sh, relu);
-    return fmaf(-k2, yv - mean, fmaf(sc, m, -k1));
-  };
-  const int64_t stride = (int64_t)gridDim.x * 256;
-  if ((((uintptr_t)pg | (uintptr_t)py | (uintptr_t)po) & 15) == 0 && (S & 3) == 0) {
-    const int64_t n4 = S >> 2;
-    const float4* g4 = reinterpret_cast<const float4*>(pg);
-    const float4* y4 = reinterpret_cast<const float4*>(py);
-    float4* o4 = reinterpret_cast<float4*>(po);
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
-      const float4 a = g4[i], b = y4[i];
-      float4 v;
-      v.x = one(a.x, b.x);
-      v.y = one(a.y, b.y);
-      v.z = one(a.z, b.z);
-      v.w = one(a.w, b.w);
-      o4[i] = v;
-    }
-  } else {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < S; i += stride) po[i] = one(pg[i], py[i]);
-  }
-}
-
 // The coefficients and the apply pass in ONE launch: every block of (n, c) first adds its statistic group's partial
 // rows exactly as bn_bwd_coeffs_kernel does (64 slices, slice order: the same bits), then streams its elements.  Block
 // (0, c, 0) also writes dgamma[c] / dbeta[c] (the sums over all S groups).  entries = sps * T partial rows per group is
@@ -723,19 +685,6 @@ int pf_edge_backward_coeffs_f32(const double* partials, int G, int T, int cbn, i
   hipLaunchKernelGGL(edge_bwd_coeffs_kernel, dim3((unsigned)pf_cdiv(cbn, 4)), dim3(256), 0, (hipStream_t)stream,
                      partials, G / groups_per_stat, groups_per_stat, T, cbn, concat ? C : 0, points, points * k, c1, c2,
                      dgamma, dbeta, accumulate);
-  return pf_launch_status();
-}
-
-int pf_bn_bwd_apply_f32(const float* g, const float* y, const float* rows, const float* coef, float* dy, int64_t N,
-                        int64_t C, int64_t S, int samples_per_stat, int relu, void* stream) {
-  PF_REQUIRE(N >= 0 && C >= 0 && S >= 0 && N <= 65535 && C <= 65535 && samples_per_stat >= 1);
-  if (N == 0 || C == 0 || S == 0) return PF_OK;
-  PF_REQUIRE(g && y && rows && coef && dy);
-  int64_t blocks = (S / 4 + 255) / 256;
-  blocks = blocks < 1 ? 1 : (blocks > 64 ? 64 : blocks);
-  dim3 grid((unsigned)blocks, (unsigned)C, (unsigned)N);
-  hipLaunchKernelGGL(bn_bwd_apply_kernel, grid, dim3(256), 0, (hipStream_t)stream, g, y, rows, coef, dy, (int)C, S,
-                     samples_per_stat, relu);
   return pf_launch_status();
 }
 

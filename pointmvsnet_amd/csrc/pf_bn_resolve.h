@@ -14,10 +14,7 @@
 
 // A pending BatchNorm handed to its CONSUMER (`in_bn` of pf_conv2d_wide_f32 / pf_pointwise_gemm_f32 /
 // pf_flow_head_f32, resolved per block by pf_bn_resolve below): the job must describe finished statistics rows.
-#ifndef PF_RESOLVE_BATCH
-#define PF_RESOLVE_BATCH 5
-#endif
-constexpr int kResolveBatch = PF_RESOLVE_BATCH;
+constexpr int kResolveBatch = 5;
 constexpr int kResolveMaxRows = 4096;   // rows behind one statistic; beyond that the re-reduction per block is absurd
 static inline int pf_bn_in_check(const pf_bn_job* j, int C, int stat_groups) {
   PF_REQUIRE(j != nullptr && j->partials != nullptr && j->gamma != nullptr && j->beta != nullptr);

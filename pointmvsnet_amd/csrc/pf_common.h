@@ -64,49 +64,20 @@ static inline int pf_zero_async(void* p, size_t bytes, hipStream_t s) {
 
 // ---- XCD-aware block order ------------------------------------------------------------------------
 // Workgroups are dealt to the 8 XCDs round-robin in dispatch order (linear block id % 8) and every XCD has its own 4 MB
-// L2.  With tile = block, the eight neighbours of a tile -- which read the same halo rows / gather the same point rows --
-// sit on eight different L2s.  pf_xcd_chunk relabels the blocks so that XCD x owns the x-th contiguous eighth of the
-// launch's tiles: neighbours share an L2.  A pure relabelling (a bijection of the grid): results are bit-identical as long
-// as everything a kernel derives from blockIdx -- the BatchNorm partial row included -- comes from the relabelled ids.
-// PF_XCD is a bit mask of kernel families (tools/experiments/build_xcd_variants.sh: A/B builds); 0 = tile = block
-// everywhere.  Measured same-box on the headline (profiles/r06t_xcd_block_order.md): towers +1.0 %, conv3d -0.6 %, flow
-// feature assembly +-0, the coarse warp by pixel-row bands (bit 32) +0.4 % inside the spread -- so only the towers take it by default.  (The EdgeConv gather passes use their own band order,
-// csrc/edgeconv.hip: xcd_tile, +2.3 %.)
-#ifndef PF_XCD
-#define PF_XCD 1
-#endif
-#define PF_XCD_TOWER 1
-#define PF_XCD_CONV3D 2
-#define PF_XCD_FETCH 4
-#define PF_XCD_KNN 8
-#define PF_XCD_EDGE 16
-#define PF_XCD_FRUSTUM 32
+// L2.  With tile = block, the eight neighbours of a tile -- which read the same halo rows -- sit on eight different L2s.
+// pf_xcd_xy relabels the blocks of a 2-D grid so that XCD x owns the x-th contiguous eighth of the launch's tiles:
+// neighbours share an L2.  A pure relabelling (a bijection of the grid): results are bit-identical as long as everything
+// a kernel derives from blockIdx -- the BatchNorm partial row included -- comes from the relabelled ids.  The tower
+// convolutions (conv2d_wide.hip) take it: +1.0 % on the headline; the other kernel families measured showed nothing or
+// lost (profiles/r06t_xcd_block_order.md).  (The EdgeConv gather passes use their own band order, edgeconv.hip: xcd_tile.)
 #ifdef __HIPCC__
-__device__ __forceinline__ unsigned pf_xcd_chunk(unsigned lin, unsigned total) {
+// the relabelled (blockIdx.x, blockIdx.y) of a 2-D grid (x fastest in dispatch order)
+__device__ __forceinline__ void pf_xcd_xy(unsigned& bx, unsigned& by) {
+  const unsigned gx = gridDim.x, total = gx * gridDim.y;
+  const unsigned lin = blockIdx.y * gx + blockIdx.x;
   const unsigned per = total >> 3, rem = total & 7u;
   const unsigned x = lin & 7u, j = lin >> 3;
-  return x * per + (x < rem ? x : rem) + j;
-}
-// Band order for point tiles of a D x (H x W) volume (tile = `unit` consecutive points, x fastest, then y, then d): XCD x owns
-// the x-th eighth of EVERY plane's tiles -- a band of pixel rows at all depths -- instead of every eighth tile.  Needs whole
-// tiles per plane and a multiple of 8 of them (else: identity).
-__device__ __forceinline__ unsigned pf_xcd_band(unsigned b, unsigned tiles_per_plane) {
-  if ((tiles_per_plane & 7u) != 0u) return b;
-  const unsigned band = tiles_per_plane >> 3;
-  const unsigned x = b & 7u, j = b >> 3;
-  const unsigned d = j / band, o = j - d * band;
-  return d * tiles_per_plane + x * band + o;
-}
-// the relabelled (blockIdx.x, blockIdx.y) of a 2-D grid (x fastest in dispatch order)
-template <int FAMILY>
-__device__ __forceinline__ void pf_xcd_xy(unsigned& bx, unsigned& by) {
-  if ((PF_XCD & FAMILY) == 0) {
-    bx = blockIdx.x;
-    by = blockIdx.y;
-    return;
-  }
-  const unsigned gx = gridDim.x;
-  const unsigned L = pf_xcd_chunk(blockIdx.y * gx + blockIdx.x, gx * gridDim.y);
+  const unsigned L = x * per + (x < rem ? x : rem) + j;
   by = L / gx;
   bx = L - by * gx;
 }

@@ -14,6 +14,10 @@ import torch
 from .. import _lib
 
 _SUFFIX = {torch.float32: "f32", torch.float64: "f64"}
+# True: the backward gathers over the inverted index lists (bit-reproducible) wherever their 32-bit pair ids reach;
+# False: always the reference's float atomics, the fallback beyond that reach (module attribute for the test that
+# compares the two, not an environment switch)
+DETERMINISTIC_BACKWARD = True
 
 
 def _check(feature_like, index, ndim, what):
@@ -55,9 +59,9 @@ class _Ext(object):
         grad_in = torch.empty((B, C, N), dtype=g.dtype, device=g.device)
         with _lib.on_device(g.device):
             # (default: the scatter as a gather over the inverted index lists -- bit-reproducible; the reference's
-            # float atomics when pointflow.DETERMINISTIC_BACKWARD is off)
+            # float atomics when DETERMINISTIC_BACKWARD is off or the lists cannot index the pairs)
             from .. import pointflow
-            det = pointflow.DETERMINISTIC_BACKWARD and B * N * K > 0 and B * N * K < 2 ** 32 - 1 and C <= 65535
+            det = DETERMINISTIC_BACKWARD and B * N * K > 0 and B * N * K < 2 ** 32 - 1 and C <= 65535
             order, start = pointflow.knn_inverse(idx, B, N, K) if det else (None, None)
             _lib.call("pf_gather_knn_backward_" + _SUFFIX[g.dtype], _lib.ptr(g), _lib.ptr(idx), _lib.ptr(grad_in),
                       B, C, N, K, _lib.ptr(order), _lib.ptr(start), _lib.stream(),

@@ -349,3 +349,27 @@ def test_flat_rmsprop_state_is_interchangeable_with_torch_rmsprop():
     flat.param_groups[0]["maximize"] = True
     with pytest.raises(NotImplementedError):
         flat._hyper()
+
+
+def test_environment_knobs_read_by_the_package_are_the_ones_design_md_lists():
+    """Every PF_* name in a getenv( / environ read under pointmvsnet_amd/ is listed in DESIGN.md section 10's knob
+    paragraph (between the knobs:begin / knobs:end markers) and the paragraph lists nothing else -- a new switch has to
+    be written down, a removed one crossed out.  The tests' and the benchmark's own names are not the package's."""
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    theirs = re.compile(r"PF_(TEST_|EMULATE$|EXPERIMENTS_|BENCH_|MIOPEN_FIND$|TRAIN_BLOCK_CONFIG$)")
+    read = set()
+    for dirpath, _, files in os.walk(os.path.join(root, "pointmvsnet_amd")):
+        for f in files:
+            if f.endswith((".py", ".hip", ".h")):
+                for line in open(os.path.join(dirpath, f)):
+                    if "getenv(" in line or "environ" in line:
+                        read.update(re.findall(r"\bPF_[A-Z0-9_]+", line))
+    design = open(os.path.join(root, "DESIGN.md")).read()
+    paragraphs = re.findall(r"<!-- knobs:begin.*?-->(.*?)<!-- knobs:end -->", design, re.S)
+    assert len(paragraphs) == 1
+    listed = set(re.findall(r"\bPF_[A-Z0-9_]+", paragraphs[0]))
+    read = {k for k in read if not theirs.match(k)}
+    listed = {k for k in listed if not theirs.match(k)}
+    assert read and read == listed, (sorted(read - listed), sorted(listed - read))
+    assert sorted(k for k in read if k.startswith("PF_DECONV_")) == ["PF_DECONV_MFMA", "PF_DECONV_VALU"]

@@ -1,4 +1,4 @@
-# round-6 job o: scene lanes in flight re-tuned after the occupancy change (PF_RESOLVE_BATCH 5)
+# round-6 job o: scene lanes in flight re-tuned after the occupancy change (pf_bn_resolve.h: kResolveBatch 5)
 cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out; export TMPDIR=/tmp; : > gpurun_out/lanes_ab.log
 for rep in 1 2; do for l in 4 3 5 6 8; do
 echo "== lanes $l (rep $rep)" >> gpurun_out/lanes_ab.log

@@ -30,7 +30,7 @@ ENTRY_KERNELS = {
     "pf_frustum_variance_cl_f32": "frustum_variance_cl_kernel", "pf_nchw_to_nhwc_f32": "nchw_to_nhwc_kernel",
     "pf_flow_pyramid_f32": "pyramid_resize_kernel", "pf_deconv3d_k3s2_f32": "deconv3d_k3s2_kernel",
     "pf_channel_bn_fused_f32": "channel_bn_fused_kernel", "pf_channel_bn_apply_f32": "channel_bn_apply_kernel",
-    "pf_channel_stats_f32": "channel_stats_kernel", "pf_bn_finalize_f32": "bn_finalize_kernel", "pf_bn_finalize_jobs_f32": "bn_finalize_kernel",
+    "pf_channel_stats_f32": "channel_stats_kernel", "pf_bn_finalize_jobs_f32": "bn_finalize_kernel",
     "pf_resize_bilinear_f32": "resize_bilinear_kernel", "pf_softargmin_prob_f32": "softargmin_prob_kernel",
     "pf_flow_head_f32": "flow_head_kernel", "pf_channel_affine_f32": "channel_affine_kernel",
 }
