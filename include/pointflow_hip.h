@@ -892,7 +892,9 @@ int pf_pack_gather_f32(const void* table, int npacks, long long max_total, void*
  * One or two launches each where autograd makes 15-25 element-wise ATen launches; float64 fixed-order reductions.
  *
  * pf_softargmin_backward_f32: backward of row S's depth (reference model.py:117-124): gcost[b,k,i] =
- *   -gdepth[b,i] * p_k * (z_k - depth[b,i]) with p = softmax(-cost) recomputed as pf_softargmin_prob_f32 rounds it.
+ *   -gdepth[b,i] * p_k * (z_k - depth[b,i]) with p = softmax(-cost) recomputed as pf_softargmin_prob_f32 rounds it and
+ *   z_k - depth evaluated as step * (k - sum_j p_j j) (no difference of two numbers of the size of the depth; the
+ *   `depth` argument must be valid and is not read).
  * pf_flow_head_train_f32: act (5*hw, ld >= 16) rows (row = d*hw + pixel) -> logit = act . w16 (channel order),
  *   prob (5, hw) = softmax(-logit) over d, offset (hw) = sum_d prob_d * (d - 2) * interval[0] (model.py:40-43,218-227).
  * pf_flow_head_backward_f32: gact (5*hw, 16) = d offset / d act * goffset, gw16 (16) (+)= its weight gradient;

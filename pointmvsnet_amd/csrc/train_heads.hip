@@ -17,10 +17,12 @@
 
 namespace {
 
-__device__ __forceinline__ float linspace_at(float start, float end, float step, int k, int D) {
-  // ATen linspace: start + step*k below the midpoint, end - step*(D-1-k) above it (as csrc/fetch.hip)
-  return (k < D / 2) ? (start + step * (float)k) : (end - step * (float)(D - 1 - k));
-}
+// z_k - depth of the backward, z the linspace of the D planes and depth = sum_j p_j z_j:  step * (k - sum_j p_j j).
+// Written on the plane INDEX, not as linspace_k - depth[pixel]: z and depth are ~5e2 with a float32 spacing of 3e-5, their
+// difference is a few `step`s, and the forward's depth carries its own rounding -- the difference of the two float32
+// numbers was off by up to 1e-4 absolute, 4e-5 of the largest gradient entry at D = 3 (against float64; 2e-6 at D = 48,
+// where the range is 16 times wider).  `mean` = sum_j p_j j is exact to float32 rounding of numbers <= D.
+__device__ __forceinline__ float softargmin_plane_offset(float step, int k, float mean) { return step * ((float)k - mean); }
 
 // one thread per pixel: softmax(-cost) recomputed exactly as the forward kernel rounds it (max, sum of expf, quotient).
 // DT = the number of depth planes at compile time (48: BASELINE configs 2 and 4; 96: config 3) or 0 (any D, below).
@@ -30,7 +32,6 @@ __device__ __forceinline__ float linspace_at(float start, float end, float step,
 template <int DT>
 __global__ __launch_bounds__(64) void softargmin_bwd_fixed_kernel(const float* __restrict__ cost,
                                                                   const float* __restrict__ params,
-                                                                  const float* __restrict__ depth,
                                                                   const float* __restrict__ gdepth,
                                                                   float* __restrict__ gcost, int64_t HW) {
   constexpr int D = DT;
@@ -55,14 +56,19 @@ __global__ __launch_bounds__(64) void softargmin_bwd_fixed_kernel(const float* _
     part[k / dq] += cv[k];
   }
   const float den = ((part[0] + part[1]) + part[2]) + part[3];
-  const float dep = depth[b * HW + i], g = gdepth[b * HW + i];
+  const float g = gdepth[b * HW + i];
+  float mean = 0.0f;                                   // sum_k p_k k: see softargmin_plane_offset
 #pragma unroll
-  for (int k = 0; k < D; ++k) gc[(int64_t)k * HW] = -g * (cv[k] / den) * (linspace_at(start, end, step, k, D) - dep);
+  for (int k = 0; k < D; ++k) {
+    cv[k] = cv[k] / den;
+    mean = fmaf(cv[k], (float)k, mean);
+  }
+#pragma unroll
+  for (int k = 0; k < D; ++k) gc[(int64_t)k * HW] = -g * cv[k] * softargmin_plane_offset(step, k, mean);
 }
 
 __global__ __launch_bounds__(256) void softargmin_bwd_kernel(const float* __restrict__ cost,
                                                              const float* __restrict__ params,
-                                                             const float* __restrict__ depth,
                                                              const float* __restrict__ gdepth,
                                                              float* __restrict__ gcost, int D, int64_t HW) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -80,10 +86,12 @@ __global__ __launch_bounds__(256) void softargmin_bwd_kernel(const float* __rest
   for (int q = 0; q < 4; ++q)
     for (int k = q * dq; k < min(D, (q + 1) * dq); ++k) part[q] += expf(-c[(int64_t)k * HW] - mx);
   const float den = ((part[0] + part[1]) + part[2]) + part[3];
-  const float dep = depth[b * HW + i], g = gdepth[b * HW + i];
+  const float g = gdepth[b * HW + i];
+  float mean = 0.0f;
+  for (int k = 0; k < D; ++k) mean = fmaf(expf(-c[(int64_t)k * HW] - mx) / den, (float)k, mean);
   for (int k = 0; k < D; ++k) {
     const float p = expf(-c[(int64_t)k * HW] - mx) / den;
-    gc[(int64_t)k * HW] = -g * p * (linspace_at(start, end, step, k, D) - dep);
+    gc[(int64_t)k * HW] = -g * p * softargmin_plane_offset(step, k, mean);
   }
 }
 
@@ -99,28 +107,31 @@ __global__ __launch_bounds__(256) void flow_head_train_kernel(const float* __res
   float wv[16];
 #pragma unroll
   for (int c = 0; c < 16; ++c) wv[c] = w[c];
-  float lg[5];
+  // The logits are summed in float64 (the products of two floats are exact there) and only the DIFFERENCE to the largest
+  // one is rounded to float32: a float32 logit of size 100 is uncertain by 16 roundings of 4e-6 each, which the softmax turns
+  // into a probability error of that size (2e-6 measured against float64 with |logit| <= 100; 1e-7 with logits of order 1).
+  double lg[5];
 #pragma unroll
   for (int d = 0; d < 5; ++d) {
     const float4* row = reinterpret_cast<const float4*>(act + ((int64_t)d * hw + p) * ld);
-    float s = 0.0f;
+    double s = 0.0;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const float4 v = row[q];
-      s += v.x * wv[4 * q];
-      s += v.y * wv[4 * q + 1];
-      s += v.z * wv[4 * q + 2];
-      s += v.w * wv[4 * q + 3];
+      s += (double)v.x * (double)wv[4 * q];
+      s += (double)v.y * (double)wv[4 * q + 1];
+      s += (double)v.z * (double)wv[4 * q + 2];
+      s += (double)v.w * (double)wv[4 * q + 3];
     }
     lg[d] = -s;
   }
-  float mx = lg[0];
+  double mx = lg[0];
 #pragma unroll
-  for (int d = 1; d < 5; ++d) mx = fmaxf(mx, lg[d]);
+  for (int d = 1; d < 5; ++d) mx = fmax(mx, lg[d]);
   float e[5], den = 0.0f;
 #pragma unroll
   for (int d = 0; d < 5; ++d) {
-    e[d] = expf(lg[d] - mx);
+    e[d] = expf((float)(lg[d] - mx));
     den += e[d];
   }
   const float iv = interval[0];
@@ -342,16 +353,16 @@ int pf_softargmin_backward_f32(const float* cost, const float* params, const flo
   if (D == 48 || D == 96) {
     dim3 grid64((unsigned)pf_cdiv(HW, 64), (unsigned)B);
     if (D == 48)
-      hipLaunchKernelGGL(softargmin_bwd_fixed_kernel<48>, grid64, dim3(64), 0, (hipStream_t)stream, cost, params, depth,
-                         gdepth, gcost, HW);
+      hipLaunchKernelGGL(softargmin_bwd_fixed_kernel<48>, grid64, dim3(64), 0, (hipStream_t)stream, cost, params, gdepth,
+                         gcost, HW);
     else
-      hipLaunchKernelGGL(softargmin_bwd_fixed_kernel<96>, grid64, dim3(64), 0, (hipStream_t)stream, cost, params, depth,
-                         gdepth, gcost, HW);
+      hipLaunchKernelGGL(softargmin_bwd_fixed_kernel<96>, grid64, dim3(64), 0, (hipStream_t)stream, cost, params, gdepth,
+                         gcost, HW);
     return pf_launch_status();
   }
   dim3 grid((unsigned)pf_cdiv(HW, 256), (unsigned)B);
-  hipLaunchKernelGGL(softargmin_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, cost, params, depth, gdepth,
-                     gcost, (int)D, HW);
+  hipLaunchKernelGGL(softargmin_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, cost, params, gdepth, gcost,
+                     (int)D, HW);
   return pf_launch_status();
 }
 

@@ -6,6 +6,8 @@ products accumulated in float32 MFMA chains per block and added in a fixed order
 tensor's largest entry; data gradients and BatchNorm gradients at 1e-5 / 2e-5.  Every result is produced twice and
 must be bit-identical (no atomics anywhere in the step).
 """
+import math
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -663,10 +665,13 @@ def test_soft_argmin_node_vs_float64_autograd(dev):
     """train_ops.soft_argmin_train (row S's kernel + pf_softargmin_backward_f32) against the reference's composition
     softmax(-cost) -> sum_k linspace_k p_k (model.py:117-124) in float64; the probability map against
     functions.get_propability_map through the inference kernel's own tests (tests/test_gpu_ops.py)."""
-    B, D, H, W = 2, 48, 16, 20
-    cost = _seeded((B, D, H, W), dev, 31, 2.0)
-    start = torch.tensor([425.0, 500.0], device=dev)
-    interval = torch.tensor([2.5, 3.0], device=dev)
+    _soft_argmin_node_case(dev, 2, 48, 16, 20, 2.0, "train_soft_argmin_node")
+
+
+def _soft_argmin_node_case(dev, B, D, H, W, cost_scale, name):
+    cost = _seeded((B, D, H, W), dev, 31, cost_scale)
+    start = torch.tensor([425.0, 500.0], device=dev)[:B]
+    interval = torch.tensor([2.5, 3.0], device=dev)[:B]
     end = start + (D - 1) * interval
     params = torch.stack([start, end, interval], dim=1).contiguous()
     g = _seeded((B, 1, H, W), dev, 32)
@@ -682,10 +687,40 @@ def test_soft_argmin_node_vs_float64_autograd(dev):
     p = F.softmax(-xr, dim=1)
     dr = (z.view(B, D, 1, 1) * p).sum(dim=1, keepdim=True)
     (dr * g.double()).sum().backward()
-    e_d, e_g = _rel(depth, dr), _rel(x.grad, xr.grad)
-    report("train_soft_argmin_node", depth=e_d, grad=e_g)
     assert not prob.requires_grad and prob.shape == depth.shape
+    assert bool(torch.isfinite(depth).all()) and bool(torch.isfinite(x.grad).all()) and bool(torch.isfinite(prob).all())
+    e_d = _rel(depth, dr)
+    if D == 1:                                  # one plane: p = 1, z - depth = 0: the gradient is identically zero on both sides
+        assert bool((xr.grad == 0).all()) and bool((x.grad == 0).all())
+        report(name, depth=e_d, grad=0.0)
+        assert e_d < 2e-6, e_d
+        return x.grad, xr.grad
+    e_g = _rel(x.grad, xr.grad)
+    report(name, depth=e_d, grad=e_g)
     assert e_d < 2e-6 and e_g < 1e-5, (e_d, e_g)
+    return x.grad, xr.grad
+
+
+@pytest.mark.parametrize("B,D,H,W", [(2, 48, 16, 20), (1, 96, 9, 13), (2, 8, 5, 7), (1, 5, 3, 3), (2, 1, 4, 4), (1, 3, 8, 8)])
+def test_soft_argmin_node_every_arm_vs_float64_autograd(dev, B, D, H, W):
+    """The three arms of pf_softargmin_backward_f32 -- D = 48 and D = 96 at compile time (BASELINE configs 2 / 4 and 3), any
+    D at run time -- and the forward's four depth slices at D not a multiple of 4, D < 4 and D = 1, HW not a multiple of
+    the 64 (fixed) / 256 (generic) pixels of a block: the body and the gates of the test above (the arithmetic per element
+    is the same in all three arms)."""
+    _soft_argmin_node_case(dev, B, D, H, W, 2.0, "train_soft_argmin_node_D%d_hw%d" % (D, H * W))
+
+
+@pytest.mark.parametrize("D", [48, 7])
+def test_soft_argmin_node_saturated_costs(dev, D):
+    """Costs of the order of 2e3: one plane holds all the mass at most pixels and exp(-cost) without the max-subtraction
+    would overflow float32 (-cost reaches +5e3).  Finite outputs; depth and gradient within the gates of the test above (the
+    gradient relative to the float64 gradient's largest entry, as there); and at a pixel where the float64 gradient is
+    zero on every plane the kernel's is zero on every plane too."""
+    got, ref = _soft_argmin_node_case(dev, 2, D, 9, 13, 2.0e3, "train_soft_argmin_saturated_D%d" % D)
+    dead = (ref.abs().amax(dim=1, keepdim=True) == 0).expand_as(ref)
+    assert bool((got[dead] == 0).all())
+    one_hot = F.softmax(-_seeded((2, D, 9, 13), dev, 31, 2.0e3).double(), dim=1).amax(dim=1) > 1.0 - 1e-6
+    assert float(one_hot.double().mean()) > 0.5                   # "most pixels" are saturated
 
 
 def test_flow_head_node_vs_float64_autograd(dev):
@@ -718,12 +753,146 @@ def test_flow_head_node_vs_float64_autograd(dev):
     assert errs["offset"] < 5e-6 and errs["prob"] < 2e-6 and errs["gact"] < 1e-5 and errs["gw"] < 1e-5, errs
 
 
-@pytest.mark.parametrize("B,h,w,H,W", [(1, 128, 160, 512, 640), (2, 7, 9, 30, 37), (1, 64, 80, 512, 640)])
+@pytest.mark.parametrize("hw,saturated", [(1, False), (255, False), (256, False), (257, False), (1517, False), (4097, False),
+                                          (257, True), (1517, True)])
+def test_flow_head_c_abi_every_block_count(dev, hw, saturated):
+    """pf_flow_head_train_f32 / pf_flow_head_backward_f32 called directly: 1 .. 17 blocks of 256 pixels (17: the weight-sum
+    slices, 16 of them, take a second block), the activations as the first 16 columns of a (5 hw, 32) buffer (ld = 32,
+    NaN in the other 16), accumulate = 0 and accumulate = 1 into a pre-filled gw16; `saturated`: activations scaled so
+    that |logit| reaches 100 (a one-hot softmax at more than a third of the pixels).  The four gates of the node test above; accumulate = 1
+    equals pre-fill + the accumulate = 0 result within one float32 rounding of the sum."""
+    gen = torch.Generator().manual_seed(1000 + hw)
+    w16 = (torch.rand(16, generator=gen) - 0.5) * 0.5
+    act = torch.relu(torch.randn((5 * hw, 16), generator=gen)) + 0.01
+    if saturated:
+        act = act * (100.0 / float((act.double() @ w16.double()).abs().max()))
+    interval = torch.tensor([1.9])
+    g = torch.randn((hw,), generator=gen)
+    buf = torch.full((5 * hw, 32), float("nan"))
+    buf[:, :16] = act
+    d_buf, d_w, d_iv, d_g = buf.to(dev), w16.to(dev), interval.to(dev), g.to(dev)
+    offset = torch.full((hw,), float("nan"), device=dev)
+    prob = torch.full((5, hw), float("nan"), device=dev)
+    _lib.call("pf_flow_head_train_f32", _lib.ptr(d_buf), 32, _lib.ptr(d_w), _lib.ptr(d_iv), hw, _lib.ptr(offset),
+              _lib.ptr(prob), _lib.stream())
+    nbytes = int(_lib.load().pf_flow_head_backward_workspace(hw))
+    assert nbytes == 8 * 16 * ((hw + 255) // 256)
+    pre = torch.randn(16, generator=gen)
+    outs = []
+    for accumulate in (0, 1, 1):
+        work = torch.full((nbytes // 8,), float("nan"), dtype=torch.float64, device=dev)
+        gact = torch.full((5 * hw, 16), float("nan"), device=dev)
+        gw = pre.clone().to(dev) if accumulate else torch.full((16,), float("nan"), device=dev)
+        _lib.call("pf_flow_head_backward_f32", _lib.ptr(d_buf), 32, _lib.ptr(d_w), _lib.ptr(d_iv), _lib.ptr(prob), _lib.ptr(d_g),
+                  hw, _lib.ptr(gact), _lib.ptr(gw), accumulate, _lib.ptr(work), nbytes, _lib.stream())
+        torch.cuda.synchronize()
+        outs.append((gact.cpu(), gw.cpu()))
+    (ga0, gw0), (ga1, gw1), (ga2, gw2) = outs
+    assert torch.equal(ga0, ga1) and torch.equal(ga1, ga2) and torch.equal(gw1, gw2)
+    want = pre.double() + gw0.double()
+    assert bool(((gw1.double() - want).abs() <= 2.0 ** -24 * want.abs()).all()), (gw1, want)
+    ar = act.double().requires_grad_(True)
+    wr = w16.double().requires_grad_(True)
+    flow = (ar * wr.view(1, -1)).sum(dim=1).view(5, hw)
+    pr = F.softmax(-flow, dim=0)
+    length = torch.tensor([-2.0, -1.0, 0.0, 1.0, 2.0], dtype=torch.float64).view(5, 1) * interval.double()
+    offr = (pr * length).sum(dim=0)
+    (offr * g.double()).sum().backward()
+    if saturated:
+        assert float(flow.abs().max()) > 99.0 and float((pr.amax(dim=0) > 1.0 - 1e-6).double().mean()) > 1.0 / 3.0
+    for t in (offset, prob, ga0, gw0):
+        assert bool(torch.isfinite(t).all())
+    errs = dict(offset=_rel(offset.cpu(), offr), prob=_rel(prob.cpu(), pr), gact=_rel(ga0, ar.grad), gw=_rel(gw0, wr.grad))
+    report("train_flow_head_abi_hw%d%s" % (hw, "_saturated" if saturated else ""), **errs)
+    assert errs["offset"] < 5e-6 and errs["prob"] < 2e-6 and errs["gact"] < 1e-5 and errs["gw"] < 1e-5, errs
+
+
+@pytest.mark.parametrize("wd", [False, True])
+@pytest.mark.parametrize("n", [1, 3, 5, 1023, 4096])
+def test_rmsprop_kernel_vs_float64_formula(dev, n, wd):
+    """pf_rmsprop_f32 directly, n below / across / at a multiple of its four elements per thread (the scalar tail), with and
+    without the weight-decay row, two steps, against the formula of the kernel's comment in float64:
+    g' = g + wd p;  sq = sq alpha + (1 - alpha) g'^2;  p = p - lr g' / (sqrt(sq) + eps).  The gate of
+    tests/test_gpu_model.py::test_flat_rmsprop_equals_torch_rmsprop (max |a - b| / max |b| < 2e-6, parameters and square
+    averages); the four elements after each buffer's n are not written."""
+    gen = torch.Generator().manual_seed(n)
+    GUARD = 7.25
+    lr, alpha, eps = 1e-3, 0.9, 1e-8
+    f32 = lambda v: float(torch.tensor(v, dtype=torch.float32))                               # noqa: E731
+    lr64, a64, eps64 = f32(lr), f32(alpha), f32(eps)
+
+    def padded(vals):
+        t = torch.full((n + 4,), GUARD)
+        t[:n] = vals
+        return t.to(dev)
+
+    p0 = torch.randn(n, generator=gen)
+    p, sq = padded(p0), padded(torch.zeros(n))
+    wrow = padded(torch.where(torch.rand(n, generator=gen) < 0.5, torch.tensor(0.001), torch.tensor(0.0))) if wd else None
+    p64, sq64 = p0.double(), torch.zeros(n, dtype=torch.float64)
+    worst = 0.0
+    for step in range(2):
+        grad = torch.randn(n, generator=gen) * (10.0 ** float(torch.randint(-4, 1, (1,), generator=gen)))
+        gbuf = padded(grad)
+        _lib.call("pf_rmsprop_f32", _lib.ptr(p), _lib.ptr(gbuf), _lib.ptr(sq), _lib.ptr(wrow), n, lr, alpha, eps, _lib.stream())
+        torch.cuda.synchronize()
+        gg = grad.double() + (wrow.cpu()[:n].double() * p64 if wd else 0.0)
+        sq64 = sq64 * a64 + (1.0 - a64) * gg * gg
+        p64 = p64 - lr64 * gg / (sq64.sqrt() + eps64)
+        for name, got, ref in (("p", p, p64), ("sq", sq, sq64)):
+            got = got.cpu()
+            assert bool((got[n:] == GUARD).all()), (name, "guard elements written")
+            err = float((got[:n].double() - ref).abs().max() / ref.abs().max().clamp_min(1e-20))
+            worst = max(worst, err)
+            assert err < 2e-6, (step, name, err)
+        assert bool((gbuf.cpu()[n:] == GUARD).all()) and (wrow is None or bool((wrow.cpu()[n:] == GUARD).all()))
+    report("rmsprop_kernel_n%d_wd%d" % (n, int(wd)), worst_rel=worst)
+
+
+def _masked_mae_inputs(dev, B, h, w, H, W):
+    gt = (_seeded((B, 1, H, W), dev, 51).abs() * 100 + 400)
+    gt = gt * (_seeded((B, 1, H, W), dev, 52) > -0.5).float()                   # ~30 % invalid
+    if B == 3:
+        gt[1] = 0.0                                                             # a sample without one valid pixel
+    return gt
+
+
+def _masked_mae_raw(dev, pred, gt, interval, weight):
+    """(loss, coef) of pf_masked_mae_f32 itself (the node keeps coef to itself)"""
+    B, _, h, w = pred.shape
+    H, W = gt.shape[2:]
+    loss = torch.full((), float("nan"), device=dev)
+    coef = torch.full((B,), float("nan"), device=dev)
+    p, t = pred.contiguous(), gt.contiguous()
+    _lib.call("pf_masked_mae_f32", _lib.ptr(p), _lib.ptr(t), _lib.ptr(interval), B, h, w, H, W, float(weight),
+              _lib.ptr(loss), _lib.ptr(coef), _lib.stream())
+    torch.cuda.synchronize()
+    return loss, coef
+
+
+# (B, h, w, H, W).  From (3, 7, 9, 30, 37) on: sample 1 of 3 entirely invalid (count 0: coef = weight / (interval 1e-7));
+# h w = 1024, 1023, 1025 and 4096 (the 1024-thread stride and the four-pixel trip of the loss kernel's one block; the last
+# an identity resize); a ground truth SMALLER than the prediction (h > H).
+@pytest.mark.parametrize("B,h,w,H,W", [(1, 128, 160, 512, 640), (2, 7, 9, 30, 37), (1, 64, 80, 512, 640),
+                                       (3, 7, 9, 30, 37), (1, 32, 32, 64, 64), (1, 31, 33, 64, 64), (1, 25, 41, 50, 82),
+                                       (1, 64, 64, 64, 64), (2, 9, 11, 4, 5)])
 def test_masked_mae_node_vs_float64_composition(dev, B, h, w, H, W):
     """train_ops.masked_mae against F.interpolate(gt) (nearest) + MAELoss (reference networks.py:170-181,
     model.py:308-339) in float64, ground truth with holes (zeros), a non-integer resize ratio among the cases."""
-    gt = (_seeded((B, 1, H, W), dev, 51).abs() * 100 + 400)
-    gt = gt * (_seeded((B, 1, H, W), dev, 52) > -0.5).float()                   # ~30 % invalid
+    gt = _masked_mae_inputs(dev, B, h, w, H, W)
+    _masked_mae_case(dev, gt, B, h, w, "train_masked_mae_node_%dx%d" % (h, w))
+
+
+def test_masked_mae_negative_ground_truth_counts_as_valid(dev):
+    """The mask is gt != 0 (reference networks.py:172), not gt > 0: negative entries are valid pixels."""
+    B, h, w, H, W = 2, 7, 9, 30, 37
+    gt = _masked_mae_inputs(dev, B, h, w, H, W)
+    gt = gt * torch.where(_seeded((B, 1, H, W), dev, 54) > 0.0, 1.0, -1.0)
+    assert bool((F.interpolate(gt, (h, w)) < 0).any())
+    _masked_mae_case(dev, gt, B, h, w, "train_masked_mae_node_negative_gt")
+
+
+def _masked_mae_case(dev, gt, B, h, w, name):
     pred = F.interpolate(gt, (h, w)) + _seeded((B, 1, h, w), dev, 53, 3.0)
     pred[0, 0, 0, 0] = F.interpolate(gt, (h, w))[0, 0, 0, 0]                     # an exact hit: sign(0) = 0
     interval = (torch.rand(B, device=dev) + 2.0).contiguous()
@@ -740,5 +909,15 @@ def test_masked_mae_node_vs_float64_composition(dev, B, h, w, H, W):
     ref = networks.MAELoss()(pr, target, interval.double()) * weight
     (ref * 1.7).backward()
     e_l, e_g = abs(float(loss) - float(ref)) / abs(float(ref)), _rel(p.grad, pr.grad)
-    report("train_masked_mae_node_%dx%d" % (h, w), loss=e_l, grad=e_g)
+    report(name, loss=e_l, grad=e_g)
     assert loss.shape == () and e_l < 2e-7 and e_g < 2e-7, (e_l, e_g)
+    if B == 3:
+        # sample 1 has no valid pixel: its gradient rows are exactly 0, its loss term is exactly 0 (the loss has the bits of
+        # the loss over samples 0 and 2 alone) and its coefficient weight / (interval * 1e-7) is finite
+        assert bool((target[1] == 0).all()) and bool((p.grad[1] == 0).all()) and bool(torch.isfinite(p.grad).all())
+        keep = torch.tensor([0, 2], device=dev)
+        loss3, coef3 = _masked_mae_raw(dev, pred, gt, interval, weight)
+        loss2, coef2 = _masked_mae_raw(dev, pred[keep], gt[keep], interval[keep].contiguous(), weight)
+        assert torch.equal(loss3, loss) and torch.equal(loss3, loss2) and torch.equal(coef3[keep], coef2)
+        c1, want = float(coef3[1]), weight / (float(interval[1]) * 1e-7)
+        assert math.isfinite(c1) and abs(c1 - want) <= 1e-6 * want, (c1, want)
