@@ -645,6 +645,37 @@ int pf_cloud_splat_f32(const float* points, int64_t N, const float* proj, int V,
                        float depth_max, uint64_t* zbuf, void* stream);
 int pf_cloud_zbuf_decode(const uint64_t* zbuf, int V, int h, int w, float* depth, int* index, void* stream);
 
+/* ---- meshing: TSDF integration of depth maps and marching tetrahedra (csrc/tsdf.hip) ----------------------------------
+ * Volumetric fusion and iso-surface extraction, which the reference does not have.  The specification is this project's
+ * own (pointmvsnet_amd/tsdf.py).  A volume has nx x ny x nz samples, indexed [k][j][i] (x fastest); sample (i, j, k) sits at
+ * o + (float)i * voxel per coordinate; nx * ny * nz <= PF_TSDF_MAX_SAMPLES.  proj as for pf_cloud_splat_f32.
+ * pf_tsdf_integrate_f32: per sample and view v in ascending order, in float32: qx, qy, z as in pf_cloud_splat_f32; skip
+ *   unless depth_min < z < depth_max; u = qx / z, v = qy / z; skip unless 0 <= u < w and 0 <= v < h (compared as floats);
+ *   d = depths[v][floor(v)][floor(u)]; skip unless depth_min < d < depth_max; sdf = d - z; skip if sdf < -trunc;
+ *   S += fminf(sdf, trunc) / trunc, W += 1; with images (V, h, w, 3) uint8 and |sdf| <= trunc: CS (nz, ny, nx, 3) += rgb,
+ *   CW += 1.  S, W (and CS, CW) are read and written: a call continues the sums of the calls before it.  images NULL: CS and
+ *   CW are not touched.  One thread owns a sample: no atomics, one order of summation.
+ * pf_tsdf_count_triangles: count ((nz-1)(ny-1)(nx-1)) int32, per cell (k (ny-1) + j)(nx-1) + i the number of triangles, 0..12:
+ *   0 unless all 8 corners have weight >= min_weight; a corner is inside iff tsdf < 0; the cell is cut into the tetrahedra
+ *   (0,1,3,7) (0,3,2,7) (0,2,6,7) (0,6,4,7) (0,4,5,7) (0,5,1,7) of its corners c = dx + 2 dy + 4 dz; a tetrahedron with 1 or 3
+ *   inside corners gives one triangle, with 2 two.
+ * pf_tsdf_emit_triangles: inclusive = the inclusive prefix sum of count, faces its last value; keys (faces, 3) int64: per
+ *   triangle the keys of its three edges, (sample index of the lower end) * 8 + direction bits, in the order and winding of
+ *   pointmvsnet_amd/tsdf.py (normals from inside to outside).
+ * pf_tsdf_vertices_f32: per key the vertex p_a + t (p_b - p_a), t = f_a / (f_a - f_b), per coordinate in float32; with colour
+ *   (nz, ny, nx, 3) uint8 also floor(c_a + t (c_b - c_a) + 0.5) clamped to 0..255 into colours (count, 3); both NULL or neither.
+ *   A key that names no edge of the volume (direction bits 0, an end outside the grid, no such sample) gives (0, 0, 0). */
+#define PF_TSDF_MAX_SAMPLES 2147483647LL
+int pf_tsdf_integrate_f32(const float* depths, const unsigned char* images, const float* proj, int V, int h, int w, float ox,
+                          float oy, float oz, float voxel, int nx, int ny, int nz, float trunc, float depth_min,
+                          float depth_max, float* S, int* W, int* CS, int* CW, void* stream);
+int pf_tsdf_count_triangles(const float* tsdf, const int* weight, int nx, int ny, int nz, int min_weight, int* count,
+                            void* stream);
+int pf_tsdf_emit_triangles(const float* tsdf, const int* weight, int nx, int ny, int nz, int min_weight,
+                           const int64_t* inclusive, int64_t faces, int64_t* keys, void* stream);
+int pf_tsdf_vertices_f32(const int64_t* keys, int64_t count, const float* tsdf, const unsigned char* colour, float ox, float oy,
+                         float oz, float voxel, int nx, int ny, int nz, float* vertices, unsigned char* colours, void* stream);
+
 /* ---- image preprocessing from decoded uint8 views (csrc/preprocess.hip) -----------------------------------------
  * What reference dataset.py:269-287 does on the host before it uploads float32: cv2.resize, crop_dtu_input and
  * norm_image (utils/preprocess.py:6-11,56-85).  Specification: pointmvsnet_amd/utils/preprocess.py (the resize is this

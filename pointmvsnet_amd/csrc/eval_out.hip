@@ -90,10 +90,10 @@ int pf_eval_prob_filter_f32(const float* depth, const float* flow_conf, const fl
 // A build that is not hipcc's (no __HIP__: the host re-compilation of tests/hipemu, whose list of sources is fixed) gets
 // the next stage of the evaluation output, the fusion kernels, the scene input (preprocess.hip), the point-cloud
 // evaluation (cloud_eval.hip), the scan's confidence filter (scan_filter.hip), the round-trip consistency filter
-// (geo_filter.hip), the point-cloud renderer (cloud_render.hip), the normal maps (depth_normals.hip) and the cloud cleaning
-// (cloud_filter.hip) with this unit, so that such a library exports the whole C ABI.  hipcc compiles fusion.hip,
-// preprocess.hip, cloud_eval.hip, scan_filter.hip, geo_filter.hip, cloud_render.hip, depth_normals.hip and cloud_filter.hip
-// as units of their own (build.SOURCES) and never takes this branch.
+// (geo_filter.hip), the point-cloud renderer (cloud_render.hip), the normal maps (depth_normals.hip), the cloud cleaning
+// (cloud_filter.hip) and the meshing (tsdf.hip) with this unit, so that such a library exports the whole C ABI.  hipcc
+// compiles fusion.hip, preprocess.hip, cloud_eval.hip, scan_filter.hip, geo_filter.hip, cloud_render.hip, depth_normals.hip,
+// cloud_filter.hip and tsdf.hip as units of their own (build.SOURCES) and never takes this branch.
 #if !defined(__HIP__)
 #include "fusion.hip"
 #include "preprocess.hip"
@@ -103,4 +103,5 @@ int pf_eval_prob_filter_f32(const float* depth, const float* flow_conf, const fl
 #include "cloud_render.hip"
 #include "depth_normals.hip"
 #include "cloud_filter.hip"
+#include "tsdf.hip"
 #endif

@@ -46,6 +46,7 @@ from .fusion import fuse_depth_maps
 from .geometric import geometric_filter
 from .normals import depth_normals
 from .render import depth_map_errors, render_depth_maps
+from .tsdf import TSDFVolume, dims_for, volume_bounds
 from .utils.eval_file_logger import _resize_nearest, _scene_paths
 from .utils.io import write_ply
 
@@ -164,7 +165,7 @@ class ScanAccumulator(object):
     """Collects the predictions of the ``view_num`` views of one scan on the device and turns them into the point cloud.
 
     ``add(data_batch, preds)`` after every forward; then ``filtered()``, ``cameras()``, ``normals()``, ``fuse()``,
-    ``write_ply(path)``.
+    ``write_ply(path)``, ``mesh(voxel)``, ``write_mesh(path, voxel=...)``.
     ``name`` is the depth map that is fused (``preds[name]``, ``preds[name + "_prob"]``), ``mode`` and the thresholds are
     those of ``filter_depth_maps``; ``keep_images`` keeps the views' images for the cloud's colours."""
 
@@ -321,6 +322,32 @@ class ScanAccumulator(object):
         pred = self.filtered() if filtered else self._depth
         return depth_map_errors(pred, render_depth_maps(gt_points, K, E, int(pred.shape[1]), int(pred.shape[2]), splat=splat),
                                 thresholds)
+
+    def mesh(self, voxel, trunc=None, min_weight=2, bounds=None, filtered=True, with_colour=True):
+        """``(vertices (Nv, 3) float32, faces (Nf, 3) int32, colours (Nv, 3) uint8 or None)``: the accumulated depth maps --
+        ``filtered()``, or the raw ``predictions()[0]`` with ``filtered=False`` -- integrated into a ``tsdf.TSDFVolume`` of
+        pitch ``voxel`` and truncation ``trunc`` (default ``4 * voxel``) over the box ``bounds = (lo, hi)`` (default:
+        ``tsdf.volume_bounds`` of the maps used, grown by ``trunc``), and its zero surface through the cells whose corners
+        were all seen by ``min_weight`` views (``tsdf.extract_mesh``).  Colours need the views' images."""
+        self._require_complete("mesh")
+        voxel = float(voxel)
+        trunc = 4.0 * voxel if trunc is None else float(trunc)
+        K, E = self.cameras()
+        depths = self.filtered() if filtered else self._depth
+        if bounds is None:
+            bounds = volume_bounds(depths, K, E, pad=trunc)
+        origin, dims = dims_for(bounds, voxel)
+        images = self.images() if with_colour else None
+        volume = TSDFVolume(origin, voxel, dims, trunc, with_colour=images is not None, device=depths.device)
+        volume.integrate(depths, K, E, images=images)
+        return volume.extract(min_weight)[:3]
+
+    def write_mesh(self, path, **mesh_kwargs):
+        """``mesh(**mesh_kwargs)`` written to ``path`` as a PLY with faces; returns what ``mesh`` returned."""
+        vertices, faces, colours = self.mesh(**mesh_kwargs)
+        write_ply(path, vertices.cpu().numpy(), None if colours is None else colours.cpu().numpy(),
+                  faces=faces.cpu().numpy())
+        return vertices, faces, colours
 
     def write_ply(self, path, **fuse_kwargs):
         """Fuse (``fuse_kwargs``: those of ``fuse``, ``method``, ``with_normals`` and ``clean`` among them) and write the cloud to

@@ -95,10 +95,12 @@ def write_cam_dtu(file, cam):
         f.write(cam_dtu_text(cam))
 
 
-def write_ply(file, points, colors=None, normals=None):
+def write_ply(file, points, colors=None, normals=None, faces=None):
     """Binary little-endian PLY of a point cloud: ``x y z`` float32 per vertex, then ``nx ny nz`` float32 when ``normals``
     (N, 3) is given, then ``red green blue`` uchar when ``colors`` (N, 3) is given -- the vertex layout fusibile's
-    final3d_model.ply carries; without normals, that layout minus the normals."""
+    final3d_model.ply carries; without normals, that layout minus the normals.  With ``faces`` (F, 3), integer rows into
+    ``points``, a mesh: ``element face F`` with ``property list uchar int vertex_indices`` follows the vertex element, and
+    its records (a count byte 3, three int32) the vertices; without ``faces`` the bytes are those of the cloud."""
     points = np.ascontiguousarray(points, dtype="<f4")
     if points.ndim != 2 or points.shape[1] != 3:
         raise Exception("Points must have N x 3 dimensions.")
@@ -125,9 +127,81 @@ def write_ply(file, points, colors=None, normals=None):
     if colors is not None:
         for c, n in enumerate(("red", "green", "blue")):
             vertex[n] = colors[:, c]
+    face = None
+    if faces is not None:
+        faces = np.asarray(faces)
+        if faces.ndim != 2 or faces.shape[1] != 3 or faces.dtype.kind not in "iu":
+            raise Exception("Faces must be integers with F x 3 dimensions.")
+        if faces.size and (int(faces.min()) < 0 or int(faces.max()) >= points.shape[0]):
+            raise Exception("Faces must index the points.")
+        face = np.empty(faces.shape[0], dtype=np.dtype([("n", "u1"), ("v", "<i4", (3,))]))
+        face["n"] = 3
+        face["v"] = faces
+        header += "element face %d\nproperty list uchar int vertex_indices\n"
     with open(file, "wb") as f:
-        f.write((header % points.shape[0] + "end_header\n").encode("ascii"))
+        f.write((header % ((points.shape[0],) + (() if face is None else (face.shape[0],))) + "end_header\n").encode("ascii"))
         f.write(vertex.tobytes())
+        if face is not None:
+            f.write(face.tobytes())
+
+
+def load_ply_mesh(file):
+    """``(points (N, 3) float32, colours (N, 3) uint8 or None, normals (N, 3) float32 or None, faces (F, 3) int32)`` of a
+    PLY file as ``write_ply`` writes it, with or without faces (a cloud gives ``faces`` of shape (0, 3)).  Only triangles
+    are read."""
+    with open(file, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise Exception("Not a PLY file.")
+        elements = []                                   # (name, count, [property words])
+        while True:
+            line = f.readline()
+            if not line:
+                raise Exception("Malformed PLY header.")
+            words = line.decode("ascii").split()
+            if not words or words[0] in ("comment", "obj_info"):
+                continue
+            if words == ["end_header"]:
+                break
+            if words[0] == "format" and words[1:] != ["binary_little_endian", "1.0"]:
+                raise Exception("Only binary_little_endian 1.0 PLY files are read.")
+            if words[0] == "element":
+                elements.append((words[1], int(words[2]), []))
+            if words[0] == "property" and elements:
+                elements[-1][2].append(tuple(words[1:]))
+        xyz = [("float", n) for n in "xyz"]
+        nrm = [("float", n) for n in ("nx", "ny", "nz")]
+        rgb = [("uchar", n) for n in ("red", "green", "blue")]
+        names = [e[0] for e in elements]
+        if names not in (["vertex"], ["vertex", "face"]) or elements[0][2] not in (xyz, xyz + rgb, xyz + nrm, xyz + nrm + rgb):
+            raise Exception("Only x y z float [nx ny nz float] [red green blue uchar] vertices, then faces, are read.")
+        if len(elements) == 2 and elements[1][2] not in ([("list", "uchar", "int", "vertex_indices")],
+                                                         [("list", "uchar", "int", "vertex_index")]):
+            raise Exception("Only faces of property list uchar int vertex_indices are read.")
+        count, props = elements[0][1], elements[0][2]
+        dtype = np.dtype([(n, "<f4" if t == "float" else "u1") for t, n in props])
+        blob = f.read(count * dtype.itemsize)
+        if len(blob) != count * dtype.itemsize:
+            raise Exception("Truncated PLY file.")
+        vertex = np.frombuffer(blob, dtype=dtype, count=count)
+        faces = np.zeros((0, 3), np.int32)
+        if len(elements) == 2:
+            fdtype = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
+            blob = f.read(elements[1][1] * fdtype.itemsize)
+            if len(blob) != elements[1][1] * fdtype.itemsize:
+                raise Exception("Truncated PLY file.")
+            face = np.frombuffer(blob, dtype=fdtype, count=elements[1][1])
+            if (face["n"] != 3).any():
+                raise Exception("Only triangles are read.")
+            faces = np.ascontiguousarray(face["v"], dtype=np.int32).reshape(-1, 3)
+            if faces.size and (faces.min() < 0 or faces.max() >= count):
+                raise Exception("A face indexes no vertex.")
+
+    def columns(cols, kind):
+        return np.stack([vertex[n] for n in cols], axis=1) if count else np.zeros((0, 3), kind)
+
+    have = [n for _, n in props]
+    return (columns("xyz", np.float32), columns(("red", "green", "blue"), np.uint8) if "red" in have else None,
+            columns(("nx", "ny", "nz"), np.float32) if "nx" in have else None, faces)
 
 
 def load_ply(file, return_normals=False):

@@ -5,6 +5,7 @@ preprocessing, the network, the batched confidence filter, the fusion and, optio
         [--mode LANCZOS4] [--init-prob-threshold 0.2] [--flow-prob-threshold 0.1] [--name flow2] \
         [--fusion roundtrip --num-src 10 --save-depth DIR] [--normals [--normal-step 2]] \
         [--voxel 0.2] [--outlier-radius 2.0 [--outlier-k 16] [--outlier-std 2.0] [--min-neighbors 4]] \
+        [--mesh mesh.ply --mesh-voxel 0.5 [--mesh-trunc 2.0] [--mesh-min-weight 2]] \
         [--gt stl009_total.ply --obs-mask ObsMask9_10.mat --plane Plane9.mat [--depth-errors --splat 1]]
 
 ``--weights`` is a ``torch.load``-able file: its ``"model"`` entry if it has one, a leading ``module.`` stripped from the
@@ -23,6 +24,10 @@ the dict of ``evaluate_point_cloud`` -- with cleaning of the cleaned cloud, and 
 into every view (pointmvsnet_amd/render.py, ``--splat`` pixels around each projection) and ``depth_map_errors`` of the raw and of the
 filtered depth maps against it, per view and in total, at thresholds of 1 and 3 times the reference view's depth interval
 scaled for ``--name`` as ``PointMVSNetMetric`` scales it (coarse 1, flow1 0.75, flow2 0.375).
+With ``--mesh`` the filtered depth maps are also integrated into a TSDF volume of pitch ``--mesh-voxel`` (truncation
+``--mesh-trunc``, default 4 voxels) and its zero surface through the cells seen by ``--mesh-min-weight`` views is written as a PLY
+with faces (pointmvsnet_amd/tsdf.py); the JSON line then carries ``mesh``: the grid size, the vertex and face counts and, with
+``--gt``, ``evaluate_point_cloud`` of the mesh's vertices as ``score``, next to the cloud's.
 """
 import argparse
 import json
@@ -82,6 +87,10 @@ def main():
     ap.add_argument("--outlier-k", type=int, default=16, help="statistical test: neighbours per point")
     ap.add_argument("--outlier-std", type=float, default=2.0, help="statistical test: standard deviations kept (< 0: off)")
     ap.add_argument("--min-neighbors", type=int, default=None, help="radius test: neighbours needed inside --outlier-radius")
+    ap.add_argument("--mesh", default=None, help="also write the scan as a triangle mesh (binary PLY with faces)")
+    ap.add_argument("--mesh-voxel", type=float, default=0.5, help="--mesh: the pitch of the TSDF volume")
+    ap.add_argument("--mesh-trunc", type=float, default=None, help="--mesh: the truncation distance (default: 4 voxels)")
+    ap.add_argument("--mesh-min-weight", type=int, default=2, help="--mesh: views that must have seen every corner of a cell")
     ap.add_argument("--name", default="flow2")
     ap.add_argument("--num-view", type=int, default=5)
     ap.add_argument("--height", type=int, default=960)
@@ -146,6 +155,18 @@ def main():
         out["report"] = report
     if normals is not None:
         out["normals_undefined"] = int((normals == 0).all(dim=1).sum())
+    mesh_vertices = None
+    if args.mesh:
+        from pointmvsnet_amd import tsdf
+        mesh_kwargs = {"voxel": args.mesh_voxel, "trunc": args.mesh_trunc, "min_weight": args.mesh_min_weight}
+        mesh_trunc = 4.0 * args.mesh_voxel if args.mesh_trunc is None else args.mesh_trunc
+        K, E = acc.cameras()
+        _, dims = tsdf.dims_for(tsdf.volume_bounds(filtered, K, E, pad=mesh_trunc), args.mesh_voxel)   # the grid mesh() builds
+        mesh_vertices, faces, _ = acc.write_mesh(args.mesh, **mesh_kwargs)
+        out["mesh"] = {"out": args.mesh, "voxel": args.mesh_voxel, "trunc": mesh_trunc, "min_weight": args.mesh_min_weight,
+                       "dims": list(dims), "vertices": int(mesh_vertices.shape[0]), "faces": int(faces.shape[0])}
+        print("mesh: grid %d x %d x %d, %d vertices, %d faces" % (tuple(dims) + (out["mesh"]["vertices"], out["mesh"]["faces"])),
+              file=sys.stderr)
     if args.save_depth:
         import numpy as np
         os.makedirs(args.save_depth, exist_ok=True)
@@ -166,6 +187,8 @@ def main():
         out["score"] = evaluation.evaluate_point_cloud(points, gt, **kw)
         if clean:
             out["score_before_cleaning"] = evaluation.evaluate_point_cloud(raw_points, gt, **kw)
+        if mesh_vertices is not None and mesh_vertices.shape[0]:
+            out["mesh"]["score"] = evaluation.evaluate_point_cloud(mesh_vertices, gt, **kw)
     print(json.dumps(out))
     if args.gt and args.depth_errors:
         interval = float(dataset[0]["cam_params_list"][0, 1, 3, 1]) * INTERVAL_SCALE.get(args.name, 1.0)
