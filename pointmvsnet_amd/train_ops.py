@@ -669,6 +669,11 @@ def tower_supported(tower, img):
     # the layer's input size only when that is even at every stage; other sizes take the composed ATen path
     if img.shape[-2] % 8 or img.shape[-1] % 8:
         return False
+    # per-view statistics: an (8, 8) view leaves conv3's BatchNorms ONE value per channel, where F.batch_norm raises
+    # ("Expected more than 1 value per channel when training", reference networks.py:84-124) and the rows of a single
+    # value would be var = 0: the composed path raises as the reference does
+    if (img.shape[-2] // 8) * (img.shape[-1] // 8) == 1:
+        return False
     blocks = _tower_blocks(tower)
     for i, (name, last, conv, bn) in enumerate(blocks):
         if not pointflow.conv2d_wide_supported(conv):
@@ -779,6 +784,10 @@ def volume_supported(vc, x):
         return False
     D, H, W = x.shape[2:]
     if D % 8 or H % 8 or W % 8:
+        return False
+    # one sample: an (8, 8, 8) volume leaves conv3_0 / conv3_1 ONE value per channel, where F.batch_norm raises
+    # (reference networks.py:127-167); the composed path raises as the reference does, this node would return var = 0 rows
+    if (D // 8) * (H // 8) * (W // 8) == 1:
         return False
     for name in ("conv0_1", "conv1_0", "conv2_0", "conv3_0", "conv1_1", "conv2_1", "conv3_1", "conv4_0", "conv5_0",
                  "conv6_0"):

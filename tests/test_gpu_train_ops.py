@@ -281,7 +281,18 @@ def _count_ambiguous_relu_inputs(ref):
 FLIP_GATE = 1e-1            # what flipped ReLU masks may move a gradient tensor by, relative to its largest entry
 
 
-def test_image_tower_node_vs_float64_autograd(dev, size=(64, 96), yardstick=False):
+# Input seeds of the node tests per size.  At the small sizes a gradient is decided by ReLU masks, so the float64
+# reference must have no ReLU input near zero: the seed is the one with the largest smallest |pre-activation| over every
+# BatchNorm output of the float64 ATen module, searched on the host (plain ATen, no kernel of this package involved).
+# Tower: seeds 0 .. 2543, the first to reach 1e-4.  Volume: 182 000 ReLU inputs, a minimum of 1e-4 has a chance of ~1e-6 per
+# seed; seeds 0 .. 75 135 tried, this is the best of them -- 3.6 x AMBIGUOUS, 16 x the 4.4e-6 the node deviates by.
+_TOWER_SEEDS = {(24, 40): 2529}              # smallest |pre-activation| 1.034e-4 (seed 17: 2.5e-5)
+_VOLUME_SEEDS = {(8, 24, 40): 14258}         # smallest |pre-activation| 7.25e-5 (seed 21: 2.03e-5)
+_NO_AMBIGUOUS = ((24, 40), (8, 24, 40))      # sizes at which the reference may have NO ReLU input within AMBIGUOUS of zero
+
+
+@pytest.mark.parametrize("size", [(64, 96), (24, 40)], ids=["64x96", "24x40"])
+def test_image_tower_node_vs_float64_autograd(dev, size, yardstick=False):
     """The whole ImageConv tower (eleven layers, per-view BatchNorm statistics) as ONE autograd node against the ATen
     composition in float64: the three stage outputs, every parameter gradient, the running statistics.
     (tests/test_gpu_zz_train_cfg4.py calls this at (512, 640), the size of BASELINE configs[3], with ``yardstick``: the
@@ -292,7 +303,7 @@ def test_image_tower_node_vs_float64_autograd(dev, size=(64, 96), yardstick=Fals
     ref = networks.ImageConv(8)
     ref.load_state_dict({k: v.cpu() for k, v in tower.state_dict().items()})
     ref = ref.to(dev).double().train()
-    img = _seeded((3, 3) + tuple(size), dev, 17)
+    img = _seeded((3, 3) + tuple(size), dev, _TOWER_SEEDS.get(tuple(size), 17))
     assert train_ops.tower_supported(tower, img)
     names = ("conv1", "conv2", "conv3")
     out = train_ops.tower_train(tower, img, names)
@@ -331,6 +342,7 @@ def test_image_tower_node_vs_float64_autograd(dev, size=(64, 96), yardstick=Fals
         gate = max(gate, 3.0 * yard, FLIP_GATE if amb["n"] else 0.0)
     report("tower_node" if tuple(size) == (64, 96) else "tower_node_%dx%d" % tuple(size), out_rel=worst, worst_grad_rel=errs[0][0],
            median_grad_rel=errs[len(errs) // 2][0], oracle32_worst_grad_rel=yard, ambiguous_relu_inputs=amb["n"])
+    assert tuple(size) not in _NO_AMBIGUOUS or amb["n"] == 0, amb
     assert errs[0][0] < gate, (errs[:5], yard, amb)
     for (k, a), (_, b) in zip(tower.named_buffers(), ref.named_buffers()):
         if "num_batches" in k:
@@ -342,17 +354,19 @@ def test_image_tower_node_vs_float64_autograd(dev, size=(64, 96), yardstick=Fals
     assert all(p.grad is not None for p in tower.parameters())
 
 
-def test_volume_conv_node_vs_float64_autograd(dev, size=(16, 32, 40), yardstick=False):
+@pytest.mark.parametrize("size", [(16, 32, 40), (8, 24, 40)], ids=["16x32x40", "8x24x40"])
+def test_volume_conv_node_vs_float64_autograd(dev, size, yardstick=False):
     """VolumeConv as ONE autograd node against the float64 ATen module (tests/test_gpu_zz_train_cfg4.py calls this at
     (48, 64, 80), the size of BASELINE configs[3], with ``yardstick``: the gradient gates are then tied to what the
-    oracle's own float32 evaluation deviates by, see _oracle32_yardstick)."""
+    oracle's own float32 evaluation deviates by, see _oracle32_yardstick).  (8, 24, 40): 1x3x5 at the bottom -- one
+    deep under three depth taps, the Do == 1 branch of the weight-gradient plan.)"""
     vc = networks.VolumeConv(64, 8)
     synthetic.seed_weights(vc, seed=4)
     vc = vc.to(dev).train()
     ref = networks.VolumeConv(64, 8)
     ref.load_state_dict({k: v.cpu() for k, v in vc.state_dict().items()})
     ref = ref.to(dev).double().train()
-    cost = (_seeded((1, 64) + tuple(size), dev, 21).abs()).requires_grad_(True)
+    cost = (_seeded((1, 64) + tuple(size), dev, _VOLUME_SEEDS.get(tuple(size), 21)).abs()).requires_grad_(True)
     assert train_ops.volume_supported(vc, cost)
     out = train_ops.volume_train(vc, cost)
     g = _seeded(tuple(out.shape), dev, 22)
@@ -393,6 +407,7 @@ def test_volume_conv_node_vs_float64_autograd(dev, size=(16, 32, 40), yardstick=
     report("volume_node" if tuple(size) == (16, 32, 40) else "volume_node_%dx%dx%d" % tuple(size), out_rel=e_out, dcost_rel=e_x,
            worst_grad_rel=errs[0][0], median_grad_rel=errs[len(errs) // 2][0], oracle32_dcost_rel=yard[0],
            oracle32_worst_grad_rel=yard[1], ambiguous_relu_inputs=amb["n"], dcost_frac_beyond_1e4=frac_x)
+    assert tuple(size) not in _NO_AMBIGUOUS or amb["n"] == 0, amb
     assert e_out < 2e-5 and e_x < gate_x and frac_x < 1e-2, (e_out, e_x, frac_x, yard, amb)
     assert errs[0][0] < gate_w and errs[len(errs) // 2][0] < 2e-5, (errs[:5], errs[len(errs) // 2], yard, amb)
 

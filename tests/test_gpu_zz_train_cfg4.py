@@ -233,9 +233,10 @@ def test_tower_data_gradient_at_cfg4_shape(dev, Cout, Cin, sp, k, stride, _affin
 
 
 @pytest.mark.parametrize("name,kind,Cout,Cin,sp,stride", VOLUME)
-def test_volume_data_gradient_at_cfg4_shape(dev, name, kind, Cout, Cin, sp, stride):
+def test_volume_data_gradient_at_cfg4_shape(dev, name, kind, Cout, Cin, sp, stride, tag=None, extra=None):
     """The data gradient of every VolumeConv layer through the helper _VolumeTrain.backward uses for it, against
-    autograd of F.conv3d / F.conv_transpose3d in float64."""
+    autograd of F.conv3d / F.conv_transpose3d in float64.  (tests/conv_bwd_cases.py calls this at small and ragged
+    layer-input sizes ``sp``, with its own report ``tag`` and ``extra`` report fields.)"""
     x = torch.zeros((1, Cin) + sp, dtype=torch.float64, device=dev, requires_grad=True)
     if kind == "conv":
         w = _seeded((Cout, Cin, 3, 3, 3), dev, 17, 0.1)
@@ -268,8 +269,9 @@ def test_volume_data_gradient_at_cfg4_shape(dev, name, kind, Cout, Cin, sp, stri
         dx = run()
         assert torch.equal(dx, run())
     err = _rel(dx, x.grad)
-    report("cfg4shape_volume_dgrad_%s" % name, rel=err)
+    report(tag or "cfg4shape_volume_dgrad_%s" % name, rel=err, **(extra or {}))
     assert dx.shape == x.shape and err < 1e-5, err
+    return err
 
 
 _BN_PLANAR = sorted(set(k[1] for k in EXPECTED_BN if k[0] == "planar"))
