@@ -645,6 +645,46 @@ int pf_cloud_splat_f32(const float* points, int64_t N, const float* proj, int V,
                        float depth_max, uint64_t* zbuf, void* stream);
 int pf_cloud_zbuf_decode(const uint64_t* zbuf, int V, int h, int w, float* depth, int* index, void* stream);
 
+/* ---- rasterising a triangle mesh into depth maps (csrc/mesh_render.hip) ----------------------------------------------
+ * The z-buffer above with a face for a point.  The specification is this project's own (pointmvsnet_amd/render.py, "Mesh
+ * rasterisation"); parity with OpenGL, Open3D or nvdiffrast is neither claimed nor tested.  proj and zbuf as above; h, w <=
+ * PF_MESH_MAX_SIDE; faces (Nf, 3) int32 rows of vertices (Nv, 3), Nf <= PF_MESH_MAX_FACES, Nv <= 2^31 - 1.
+ * Screen coordinates, per vertex and view in float32 in this order: qx, qy, z as in pf_cloud_splat_f32; u = qx / z,
+ *   v = qy / z; valid iff depth_min < z < depth_max and -G <= u < w + G and -G <= v < h + G, G = PF_MESH_GUARD_BAND, compared
+ *   as floats (false for NaN); xi = (int)rintf(u * 256.0f), yi = (int)rintf(v * 256.0f) (round half to even).  All that
+ *   follows is exact in int64.
+ * pf_mesh_screen_f32: that table: xy (V, Nv, 2) int32 (0, 0 where not valid), z (V, Nv) as computed, valid (V, Nv) 0 / 1.
+ *   For tests and inspection; the rasteriser re-projects with the same device function.
+ * pf_mesh_raster_f32: a face is rasterised in a view iff its three indices lie in [0, Nv) (another index is never read
+ *   through), its three vertices are valid there and area2 = (bx-ax)(cy-ay) - (by-ay)(cx-ax) != 0; no clipping.  Front-facing
+ *   iff area2 < 0; cull = PF_MESH_CULL_NONE renders both sides, PF_MESH_CULL_BACK only front-facing faces, PF_MESH_CULL_FRONT
+ *   only the others.  For area2 < 0 b and c are swapped first.  Edge p -> q, d = q - p: E(s) = dx (sy - py) - dy (sx - px);
+ *   pixel (x, y) with centre s = (256 x + 128, 256 y + 128) is covered iff for each of a -> b, b -> c, c -> a: E(s) > 0, or
+ *   E(s) == 0 and (dy > 0 or (dy == 0 and dx < 0)).  With Ea, Eb, Ec the edge functions opposite a, b, c:
+ *   ra = 1.0f / za (rb, rc likewise), inv = ((float)Ea * ra + (float)Eb * rb) + (float)Ec * rc, z = (float)area2 / inv;
+ *   zbuf[v][y][x] = min(zbuf[v][y][x], float_bits(z) << 32 | face) by a 64-bit unsigned atomic minimum.  A face whose
+ *   bounding box clamped to the map holds more than PF_MESH_LANE_PIXELS pixel centres is walked by its wave instead of its
+ *   lane; the result does not depend on that.  Decode with pf_cloud_zbuf_decode.
+ * pf_mesh_raster_tuned_f32: the same with that threshold as the argument lane_pixels >= 0 (tools/microbench_mesh_render.py).
+ * pf_mesh_bary_f32: index (V, h, w) int32 from the decode; bary (V, h, w, 3) = ((float)Ea ra / inv, (float)Eb rb / inv,
+ *   (float)Ec rc / inv) of the pixel's face in the face's STORED vertex order, zeros where index is -1. */
+#define PF_MESH_GUARD_BAND 16384
+#define PF_MESH_MAX_SIDE 16384
+#define PF_MESH_MAX_FACES 4294967294LL
+#define PF_MESH_LANE_PIXELS 64
+#define PF_MESH_CULL_NONE 0
+#define PF_MESH_CULL_BACK 1
+#define PF_MESH_CULL_FRONT 2
+int pf_mesh_screen_f32(const float* vertices, int64_t Nv, const float* proj, int V, int h, int w, float depth_min,
+                       float depth_max, int* xy, float* z, unsigned char* valid, void* stream);
+int pf_mesh_raster_f32(const float* vertices, int64_t Nv, const int* faces, int64_t Nf, const float* proj, int V, int h,
+                       int w, float depth_min, float depth_max, int cull, uint64_t* zbuf, void* stream);
+int pf_mesh_raster_tuned_f32(const float* vertices, int64_t Nv, const int* faces, int64_t Nf, const float* proj, int V, int h,
+                             int w, float depth_min, float depth_max, int cull, int lane_pixels, uint64_t* zbuf,
+                             void* stream);
+int pf_mesh_bary_f32(const float* vertices, int64_t Nv, const int* faces, int64_t Nf, const float* proj, int V, int h, int w,
+                     float depth_min, float depth_max, const int* index, float* bary, void* stream);
+
 /* ---- meshing: TSDF integration of depth maps and marching tetrahedra (csrc/tsdf.hip) ----------------------------------
  * Volumetric fusion and iso-surface extraction, which the reference does not have.  The specification is this project's
  * own (pointmvsnet_amd/tsdf.py).  A volume has nx x ny x nz samples, indexed [k][j][i] (x fastest); sample (i, j, k) sits at

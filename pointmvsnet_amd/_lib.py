@@ -122,6 +122,10 @@ PROTOTYPES = {
     "pf_cloud_voxel_reduce_f32": ([_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp], _i),
     "pf_cloud_splat_f32": ([_vp, _i64, _vp, _i, _i, _i, _i, _f, _f, _vp, _vp], _i),
     "pf_cloud_zbuf_decode": ([_vp, _i, _i, _i, _vp, _vp, _vp], _i),
+    "pf_mesh_screen_f32": ([_vp, _i64, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp], _i),
+    "pf_mesh_raster_f32": ([_vp, _i64, _vp, _i64, _vp, _i, _i, _i, _f, _f, _i, _vp, _vp], _i),
+    "pf_mesh_raster_tuned_f32": ([_vp, _i64, _vp, _i64, _vp, _i, _i, _i, _f, _f, _i, _i, _vp, _vp], _i),
+    "pf_mesh_bary_f32": ([_vp, _i64, _vp, _i64, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp], _i),
     "pf_tsdf_integrate_f32": ([_vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _f, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp], _i),
     "pf_tsdf_count_triangles": ([_vp, _vp, _i, _i, _i, _i, _vp, _vp], _i),
     "pf_tsdf_emit_triangles": ([_vp, _vp, _i, _i, _i, _i, _vp, _i64, _vp, _vp], _i),

@@ -45,7 +45,7 @@ from .cloud_filter import clean_cloud
 from .fusion import fuse_depth_maps
 from .geometric import geometric_filter
 from .normals import depth_normals
-from .render import depth_map_errors, render_depth_maps
+from .render import depth_map_errors, render_depth_maps, render_mesh_depth_maps
 from .tsdf import TSDFVolume, dims_for, volume_bounds
 from .utils.eval_file_logger import _resize_nearest, _scene_paths
 from .utils.io import write_ply
@@ -313,15 +313,28 @@ class ScanAccumulator(object):
             fused[0], fused[1], fused[2] if with_normals else None, **clean)
         return (points, colours) + ((normals,) if with_normals else ())
 
-    def depth_errors(self, gt_points, thresholds, splat=1, filtered=True):
+    def depth_errors(self, gt_points, thresholds, splat=1, filtered=True, gt_faces=None):
         """``render.depth_map_errors`` of the accumulated depth maps -- ``filtered()``, or the raw ``predictions()[0]`` with
         ``filtered=False`` -- against ``gt_points`` (N, 3) float32 on the GPU (the scan's ground-truth cloud) rendered into
-        ``cameras()`` at the depth maps' size with ``render.render_depth_maps(..., splat=splat)``."""
+        ``cameras()`` at the depth maps' size with ``render.render_depth_maps(..., splat=splat)``.  With ``gt_faces`` (Nf, 3)
+        ``gt_points`` are the vertices of the scan's ground-truth *mesh* and the ground truth is rasterised
+        (``render.render_mesh_depth_maps``; ``splat`` is ignored): no holes, and no back of the scene seen through a nearer
+        surface."""
         self._require_complete("depth_errors")
         K, E = self.cameras()
         pred = self.filtered() if filtered else self._depth
-        return depth_map_errors(pred, render_depth_maps(gt_points, K, E, int(pred.shape[1]), int(pred.shape[2]), splat=splat),
-                                thresholds)
+        h, w = int(pred.shape[1]), int(pred.shape[2])
+        if gt_faces is not None:
+            return depth_map_errors(pred, render_mesh_depth_maps(gt_points, gt_faces, K, E, h, w), thresholds)
+        return depth_map_errors(pred, render_depth_maps(gt_points, K, E, h, w, splat=splat), thresholds)
+
+    def render_mesh(self, vertices, faces, **kwargs):
+        """``render.render_mesh_depth_maps`` of a mesh into ``cameras()`` at the depth maps' size (``kwargs``: its depth
+        range, ``cull``, ``return_index``, ``return_barycentric``).  With ``mesh()``'s own vertices and faces: the fused,
+        hole-filled depth map of every view."""
+        self._require_complete("render_mesh")
+        K, E = self.cameras()
+        return render_mesh_depth_maps(vertices, faces, K, E, int(self._depth.shape[1]), int(self._depth.shape[2]), **kwargs)
 
     def mesh(self, voxel, trunc=None, min_weight=2, bounds=None, filtered=True, with_colour=True):
         """``(vertices (Nv, 3) float32, faces (Nf, 3) int32, colours (Nv, 3) uint8 or None)``: the accumulated depth maps --

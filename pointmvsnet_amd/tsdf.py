@@ -77,8 +77,8 @@ kernel over the keys.
 Out of scope
 ------------
 Sparse or hashed volumes; per-axis voxel sizes; weighting by angle or confidence; de-integration; trilinear depth
-sampling; vertex normals from the TSDF gradient; mesh simplification or smoothing; rasterising the mesh in ``render.py``;
-Poisson reconstruction.
+sampling; vertex normals from the TSDF gradient; mesh simplification or smoothing; Poisson reconstruction.  (Looking at
+the mesh from a camera is ``render.render_mesh_depth_maps``.)
 """
 import math
 

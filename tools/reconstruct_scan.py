@@ -5,8 +5,9 @@ preprocessing, the network, the batched confidence filter, the fusion and, optio
         [--mode LANCZOS4] [--init-prob-threshold 0.2] [--flow-prob-threshold 0.1] [--name flow2] \
         [--fusion roundtrip --num-src 10 --save-depth DIR] [--normals [--normal-step 2]] \
         [--voxel 0.2] [--outlier-radius 2.0 [--outlier-k 16] [--outlier-std 2.0] [--min-neighbors 4]] \
-        [--mesh mesh.ply --mesh-voxel 0.5 [--mesh-trunc 2.0] [--mesh-min-weight 2]] \
-        [--gt stl009_total.ply --obs-mask ObsMask9_10.mat --plane Plane9.mat [--depth-errors --splat 1]]
+        [--mesh mesh.ply --mesh-voxel 0.5 [--mesh-trunc 2.0] [--mesh-min-weight 2] [--save-mesh-depth DIR]] \
+        [--gt stl009_total.ply --obs-mask ObsMask9_10.mat --plane Plane9.mat [--depth-errors --splat 1]] \
+        [--gt-mesh surface.ply --depth-errors]
 
 ``--weights`` is a ``torch.load``-able file: its ``"model"`` entry if it has one, a leading ``module.`` stripped from the
 keys.  ``--fusion roundtrip`` replaces the disparity fusion by the round-trip consistency filter
@@ -27,7 +28,12 @@ scaled for ``--name`` as ``PointMVSNetMetric`` scales it (coarse 1, flow1 0.75, 
 With ``--mesh`` the filtered depth maps are also integrated into a TSDF volume of pitch ``--mesh-voxel`` (truncation
 ``--mesh-trunc``, default 4 voxels) and its zero surface through the cells seen by ``--mesh-min-weight`` views is written as a PLY
 with faces (pointmvsnet_amd/tsdf.py); the JSON line then carries ``mesh``: the grid size, the vertex and face counts and, with
-``--gt``, ``evaluate_point_cloud`` of the mesh's vertices as ``score``, next to the cloud's.
+``--gt``, ``evaluate_point_cloud`` of the mesh's vertices as ``score``, next to the cloud's.  ``--save-mesh-depth DIR`` also
+rasterises that mesh back into the scan's own views (``ScanAccumulator.render_mesh``) and writes every view's fused,
+hole-filled depth map as ``%08d_mesh.pfm``.
+With ``--gt-mesh FILE`` (a PLY with faces) ``--depth-errors`` scores against the rasterised surface instead of the splatted
+cloud: no holes, and no back of the scene seen through a nearer surface; ``--splat`` is then not used.  The line's
+``ground_truth`` names which of the two was used, ``"mesh"`` or ``"cloud"``.
 """
 import argparse
 import json
@@ -91,6 +97,7 @@ def main():
     ap.add_argument("--mesh-voxel", type=float, default=0.5, help="--mesh: the pitch of the TSDF volume")
     ap.add_argument("--mesh-trunc", type=float, default=None, help="--mesh: the truncation distance (default: 4 voxels)")
     ap.add_argument("--mesh-min-weight", type=int, default=2, help="--mesh: views that must have seen every corner of a cell")
+    ap.add_argument("--save-mesh-depth", default=None, help="--mesh: folder for every view's depth map of the mesh, %%08d_mesh.pfm")
     ap.add_argument("--name", default="flow2")
     ap.add_argument("--num-view", type=int, default=5)
     ap.add_argument("--height", type=int, default=960)
@@ -103,10 +110,13 @@ def main():
     ap.add_argument("--gt", default=None, help="the scan's ground-truth cloud (PLY): score the result")
     ap.add_argument("--obs-mask", default=None, help="DTU's ObsMask<scan>_10.mat")
     ap.add_argument("--plane", default=None, help="DTU's Plane<scan>.mat")
-    ap.add_argument("--depth-errors", action="store_true", help="with --gt: one more JSON line of per-view depth errors")
+    ap.add_argument("--gt-mesh", default=None, help="the scan's ground-truth surface (PLY with faces) for --depth-errors")
+    ap.add_argument("--depth-errors", action="store_true", help="with --gt or --gt-mesh: one more JSON line of per-view depth errors")
     ap.add_argument("--splat", type=int, default=1, help="--depth-errors: pixels around a projection that a point fills")
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args()
+    if args.save_mesh_depth and not args.mesh:
+        ap.error("--save-mesh-depth needs --mesh")
     import torch
     from pointmvsnet_amd import cloud_filter, evaluation, geometric, scan, synthetic
     from pointmvsnet_amd.dataset import DTUDataset
@@ -167,6 +177,12 @@ def main():
                        "dims": list(dims), "vertices": int(mesh_vertices.shape[0]), "faces": int(faces.shape[0])}
         print("mesh: grid %d x %d x %d, %d vertices, %d faces" % (tuple(dims) + (out["mesh"]["vertices"], out["mesh"]["faces"])),
               file=sys.stderr)
+        if args.save_mesh_depth:
+            os.makedirs(args.save_mesh_depth, exist_ok=True)
+            mesh_depth = acc.render_mesh(mesh_vertices, faces).cpu().numpy()
+            for v in range(len(dataset)):
+                io.write_pfm(os.path.join(args.save_mesh_depth, "%08d_mesh.pfm" % v), mesh_depth[v])
+            out["mesh"]["filled_share_per_view"] = [float((d > 0).mean()) for d in mesh_depth]
     if args.save_depth:
         import numpy as np
         os.makedirs(args.save_depth, exist_ok=True)
@@ -190,12 +206,24 @@ def main():
         if mesh_vertices is not None and mesh_vertices.shape[0]:
             out["mesh"]["score"] = evaluation.evaluate_point_cloud(mesh_vertices, gt, **kw)
     print(json.dumps(out))
-    if args.gt and args.depth_errors:
+    if (args.gt or args.gt_mesh) and args.depth_errors:
         interval = float(dataset[0]["cam_params_list"][0, 1, 3, 1]) * INTERVAL_SCALE.get(args.name, 1.0)
         thresholds = [interval, 3.0 * interval]
-        print(json.dumps({"scan": args.scan, "name": args.name, "splat": args.splat, "depth_interval": interval,
-                          "depth_errors_raw": acc.depth_errors(gt, thresholds, splat=args.splat, filtered=False),
-                          "depth_errors_filtered": acc.depth_errors(gt, thresholds, splat=args.splat, filtered=True)}))
+        line = {"scan": args.scan, "name": args.name, "depth_interval": interval}
+        if args.gt_mesh:                                         # the surface wins over the cloud: that is what it is for
+            import numpy as np
+            gt_vertices, _, _, gt_faces = io.load_ply_mesh(args.gt_mesh)
+            if gt_faces is None or not len(gt_faces):
+                ap.error("--gt-mesh: %s has no faces" % args.gt_mesh)
+            gt = torch.from_numpy(np.ascontiguousarray(gt_vertices, dtype=np.float32)).to(dev)
+            kw = {"gt_faces": torch.from_numpy(np.ascontiguousarray(gt_faces).astype(np.int64)).to(dev)}
+            line.update(ground_truth="mesh", gt_vertices=int(gt.shape[0]), gt_faces=int(len(gt_faces)))
+        else:
+            kw = {"splat": args.splat}
+            line.update(ground_truth="cloud", splat=args.splat)
+        line["depth_errors_raw"] = acc.depth_errors(gt, thresholds, filtered=False, **kw)
+        line["depth_errors_filtered"] = acc.depth_errors(gt, thresholds, filtered=True, **kw)
+        print(json.dumps(line))
 
 
 if __name__ == "__main__":
