@@ -357,6 +357,10 @@ int pf_channel_bn_fused_f32(const float* x, float* y, int64_t N, int64_t C, int6
  * channel is staged (zero padding after it) -- rows, or resolved by the launch itself ("the finalize folded into
  * the consumer" above); all NULL: x is taken as it is. */
 int pf_conv3d_blocks(int64_t Cin, int64_t Cout, int64_t Di, int64_t Hi, int64_t Wi, int stride);
+/* The launch plan pf_conv3d_k3_f32 uses for a shape, for tests that pin it (a pure function of the shape, computed by
+ * the function the launch itself calls): plan8 = {column tiles of 16 output channels NT, tile depth TD, tiles per
+ * sample, tiles per block, blocks per sample, dynamic LDS bytes, 0, 0}. */
+int pf_conv3d_plan(int64_t Cin, int64_t Cout, int64_t Di, int64_t Hi, int64_t Wi, int stride, int* plan8);
 int pf_conv3d_k3_f32(const float* x, const float* wp, float* y, int64_t N, int64_t Cin, int64_t Cout, int64_t Di,
                      int64_t Hi, int64_t Wi, int stride, const float* in_scale, const float* in_shift,
                      const pf_bn_job* in_bn, int samples_per_stat, double* partials, void* stream);
@@ -382,6 +386,10 @@ int pf_conv3d_k3_few_f32(const float* x, const float* w, float* y, int64_t N, in
  * layer's raw output; Cin <= 64), applied to every loaded value BEFORE the skip add -- rows, or resolved by the
  * launch itself; all NULL: xa is taken as it is. */
 int pf_deconv3d_blocks(int64_t D, int64_t H, int64_t W);
+/* The form pf_deconv3d_k3s2_f32 takes for a shape, for tests that pin it (the launch's own selection, including the
+ * environment switches PF_DECONV_MFMA / PF_DECONV_VALU): plan4 = {form (0 lane-per-cell, 1 matrix-core), output
+ * channels per block CG, blocks of 128 input cells, 0}. */
+int pf_deconv3d_plan(int64_t N, int64_t Cin, int64_t Cout, int64_t D, int64_t H, int64_t W, int* plan4);
 int pf_deconv3d_k3s2_f32(const float* xa, const float* xb, const float* w, float* y, int64_t N, int64_t Cin,
                          int64_t Cout, int64_t D, int64_t H, int64_t W, const float* in_scale, const float* in_shift,
                          const pf_bn_job* in_bn, int samples_per_stat, double* partials, void* stream);

@@ -383,41 +383,62 @@ int blocks_for(const ConvGeom& g) {
   return (int)((total + per - 1) / per);
 }
 
+// What a launch of pf_conv3d_k3_f32 does for a shape: the launch runs exactly this plan, pf_conv3d_plan reports it.
+struct ConvPlan {
+  int NT, TD;                     // column tiles of 16 output channels; tile depth (0: no tile fits the LDS)
+  int tiles, tiles_per_block, blocks;
+  size_t lds_bytes;
+  ConvGeom g;
+};
+
+ConvPlan plan_conv3d(int64_t Cin, int64_t Cout, int64_t Di, int64_t Hi, int64_t Wi, int stride) {
+  ConvPlan p{};
+  p.NT = (int)((Cout + 15) / 16);
+  p.TD = pick_td(Cin, Cout, Di, Hi, Wi, stride);
+  if (p.TD == 0) return p;
+  p.g = make_geom(Cin, Cout, Di, Hi, Wi, stride, p.TD);
+  p.tiles = p.g.tiles_d * p.g.tiles_h * p.g.tiles_w;
+  p.blocks = blocks_for(p.g);
+  p.tiles_per_block = (p.tiles + p.blocks - 1) / p.blocks;
+  p.lds_bytes = lds_bytes_for(p.g, p.NT);
+  return p;
+}
+
 template <int NT, int STRIDE, int TD, int MINW>
-int launch(const float* x, const float* wp, float* y, const ConvGeom& g, int64_t N, double* partials,
+int launch(const float* x, const float* wp, float* y, const ConvPlan& p, int64_t N, double* partials,
            hipStream_t s) {
-  const size_t lds_bytes = lds_bytes_for(g, NT);
+  const size_t lds_bytes = p.lds_bytes;
   if (lds_bytes > kMaxLds) return PF_ERR_UNSUPPORTED;
-  ConvGeom gk = g;
-  gk.aff_off = (int)(lds_work_bytes(g, NT) / sizeof(float));
+  ConvGeom gk = p.g;
+  gk.aff_off = (int)(lds_work_bytes(p.g, NT) / sizeof(float));
   if (lds_bytes > 64 * 1024) {           // opt in to more than the default 64 KiB of dynamic LDS (160 KiB per CU)
     static std::atomic<unsigned long long> done{0};   // per instantiation, one bit per device
     const int rc = pf_allow_big_lds(reinterpret_cast<const void*>(&conv3d_k3_kernel<NT, STRIDE, TD, MINW>),
                                     (int)kMaxLds, done);
     if (rc != PF_OK) return rc;
   }
-  dim3 grid((unsigned)blocks_for(g), (unsigned)N);
+  dim3 grid((unsigned)p.blocks, (unsigned)N);
   hipLaunchKernelGGL((conv3d_k3_kernel<NT, STRIDE, TD, MINW>), grid, dim3(256), lds_bytes, s, x, wp, y, gk, partials);
   return pf_launch_status();
 }
 
 template <int NT, int STRIDE, int TD>
-int launch_w(const float* x, const float* wp, float* y, const ConvGeom& g, int64_t N, double* partials,
+int launch_w(const float* x, const float* wp, float* y, const ConvPlan& p, int64_t N, double* partials,
              hipStream_t s) {
   // measured (profiles/archive/r01/r01g_microbench_conv3d.log): the 64 -> 8 layer runs 151 us at TD 4 / 2 waves per
   // SIMD and 131 us at TD 2 / 4 waves per SIMD (124 VGPRs, no spills); the stride-2 tile is best left alone
   constexpr int kDefault = (NT == 1 && STRIDE == 1 && TD == 2) ? 4 : 2;
-  return launch<NT, STRIDE, TD, kDefault>(x, wp, y, g, N, partials, s);
+  return launch<NT, STRIDE, TD, kDefault>(x, wp, y, p, N, partials, s);
 }
 
 template <int NT, int STRIDE>
-int launch_td(int td, const float* x, const float* wp, float* y, const ConvGeom& g, int64_t N, double* partials,
+int launch_td(const float* x, const float* wp, float* y, const ConvPlan& p, int64_t N, double* partials,
               hipStream_t s) {
   if constexpr (STRIDE == 1) {
-    if (td == 4) return launch_w<NT, STRIDE, 4>(x, wp, y, g, N, partials, s);
+    if (p.TD == 4) return launch_w<NT, STRIDE, 4>(x, wp, y, p, N, partials, s);
   }
-  if (td == 2) return launch_w<NT, STRIDE, 2>(x, wp, y, g, N, partials, s);
-  return launch_w<NT, STRIDE, 1>(x, wp, y, g, N, partials, s);
+  if (p.TD == 2) return launch_w<NT, STRIDE, 2>(x, wp, y, p, N, partials, s);
+  return launch_w<NT, STRIDE, 1>(x, wp, y, p, N, partials, s);
 }
 
 }  // namespace
@@ -426,9 +447,19 @@ extern "C" {
 
 int pf_conv3d_blocks(int64_t Cin, int64_t Cout, int64_t Di, int64_t Hi, int64_t Wi, int stride) {
   if (Cin <= 0 || Cout <= 0 || Di <= 0 || Hi <= 0 || Wi <= 0 || (stride != 1 && stride != 2)) return 0;
-  const int td = pick_td(Cin, Cout, Di, Hi, Wi, stride);
-  if (td == 0) return 0;
-  return blocks_for(make_geom(Cin, Cout, Di, Hi, Wi, stride, td));
+  return plan_conv3d(Cin, Cout, Di, Hi, Wi, stride).blocks;
+}
+
+int pf_conv3d_plan(int64_t Cin, int64_t Cout, int64_t Di, int64_t Hi, int64_t Wi, int stride, int* plan8) {
+  PF_REQUIRE(plan8 != nullptr && Cin >= 4 && Cout >= 1 && Di >= 1 && Hi >= 1 && Wi >= 1);
+  PF_REQUIRE(stride == 1 || stride == 2);
+  if ((Cin % 4) != 0 || Cout > 32) return PF_ERR_UNSUPPORTED;
+  PF_REQUIRE(Cin * Di * Hi * Wi <= INT32_MAX);
+  const ConvPlan p = plan_conv3d(Cin, Cout, Di, Hi, Wi, stride);
+  if (p.TD == 0) return PF_ERR_UNSUPPORTED;
+  const int out[8] = {p.NT, p.TD, p.tiles, p.tiles_per_block, p.blocks, (int)p.lds_bytes, 0, 0};
+  for (int i = 0; i < 8; ++i) plan8[i] = out[i];
+  return PF_OK;
 }
 
 int pf_conv3d_k3_f32(const float* x, const float* wp, float* y, int64_t N, int64_t Cin, int64_t Cout, int64_t Di,
@@ -447,19 +478,18 @@ int pf_conv3d_k3_f32(const float* x, const float* wp, float* y, int64_t N, int64
   PF_REQUIRE(Cin * Di * Hi * Wi <= INT32_MAX);
   if (N == 0) return PF_OK;
   PF_REQUIRE(x && wp && y);
-  const int td = pick_td(Cin, Cout, Di, Hi, Wi, stride);
-  if (td == 0) return PF_ERR_UNSUPPORTED;
-  ConvGeom g = make_geom(Cin, Cout, Di, Hi, Wi, stride, td);
+  ConvPlan plan = plan_conv3d(Cin, Cout, Di, Hi, Wi, stride);
+  if (plan.TD == 0) return PF_ERR_UNSUPPORTED;
+  ConvGeom& g = plan.g;
   g.aff_mode = in_bn ? 2 : (in_scale ? 1 : 0);
   g.sps = samples_per_stat;
   g.in_scale = in_scale;
   g.in_shift = in_shift;
   if (in_bn) g.in_bn = *in_bn;
   hipStream_t s = (hipStream_t)stream;
-  const int NT = (int)((Cout + 15) / 16);
   if (stride == 1)
-    return NT == 1 ? launch_td<1, 1>(td, x, wp, y, g, N, partials, s) : launch_td<2, 1>(td, x, wp, y, g, N, partials, s);
-  return NT == 1 ? launch_td<1, 2>(td, x, wp, y, g, N, partials, s) : launch_td<2, 2>(td, x, wp, y, g, N, partials, s);
+    return plan.NT == 1 ? launch_td<1, 1>(x, wp, y, plan, N, partials, s) : launch_td<2, 1>(x, wp, y, plan, N, partials, s);
+  return plan.NT == 1 ? launch_td<1, 2>(x, wp, y, plan, N, partials, s) : launch_td<2, 2>(x, wp, y, plan, N, partials, s);
 }
 
 int pf_conv3d_k3_few_f32(const float* x, const float* w, float* y, int64_t N, int64_t Cin, int64_t Cout, int64_t D,

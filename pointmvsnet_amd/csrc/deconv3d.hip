@@ -391,9 +391,50 @@ int launch_dm(const float* xa, const float* xb, const float* w, float* y, int64_
   return pf_launch_status();
 }
 
+// Which form a launch of pf_deconv3d_k3s2_f32 takes for a shape: the one selection both the launch and
+// pf_deconv3d_plan read.
+//
+// The matrix-core form (whole channel quads, weights of 16 output channels within 64 KB of LDS) where it was measured
+// faster (profiles/r06f_deconv_mfma.md): every block stages Cin * 27 * 16 weights, which only pays with >= 2 channel
+// groups of 16 and a grid of >= 512 blocks -- config 4's data gradient of conv1_0 (16 -> 64 on 24x32x40: 35.6 us
+// against 49.1); the decoder's 32 -> 16 and 16 -> 8 layers (30 / 240 blocks) stay on the lane-per-cell form (12.5 /
+// 10.8 us against 17.8 / 18.7).  A shape always takes the same form, so results are reproducible run to run.
+// PF_DECONV_MFMA=1 / PF_DECONV_VALU=1 force one form wherever it is valid (tests, tools/microbench_deconv3d.py).
+struct DcPlan {
+  int form;        // 0 lane-per-cell, 1 matrix-core
+  int CG;          // output channels per block: 4 / 2 / 1 (lane-per-cell), 16 (matrix-core)
+  int blocks_x;    // blocks of 128 input cells
+};
+
+DcPlan plan_deconv3d(int64_t N, int64_t Cin, int64_t Cout, int64_t D, int64_t H, int64_t W) {
+  const bool dm_ok = (Cin & 3) == 0 && Cin <= 32;
+  const bool dm_pays = Cout >= 32 && pf_cdiv(D * H * W, 128) * pf_cdiv(Cout, kDmCo) * N >= 512;
+  if (dm_ok && getenv("PF_DECONV_VALU") == nullptr && (dm_pays || getenv("PF_DECONV_MFMA") != nullptr))
+    return DcPlan{1, kDmCo, (int)pf_cdiv(D * H * W, 128)};
+  // channel group: 4 when that still leaves >= 2 blocks per CU, else 2 / 1 (more, smaller work items)
+  const int64_t cell_blocks = pf_cdiv(D * H * W, kDcThreads);
+  int cg = 1;
+  if ((Cout % 4) == 0 && cell_blocks * (Cout / 4) * N >= 512)
+    cg = 4;
+  else if ((Cout % 2) == 0 && cell_blocks * (Cout / 2) * N >= 512)
+    cg = 2;
+  return DcPlan{0, cg, (int)cell_blocks};
+}
+
 }  // namespace
 
 extern "C" {
+
+int pf_deconv3d_plan(int64_t N, int64_t Cin, int64_t Cout, int64_t D, int64_t H, int64_t W, int* plan4) {
+  PF_REQUIRE(plan4 != nullptr && N >= 1 && Cin >= 1 && Cout >= 1 && D >= 1 && H >= 1 && W >= 1 && N <= 65535);
+  PF_REQUIRE(Cin * D * H * W <= INT32_MAX && Cout <= 65535 * 4);
+  const DcPlan p = plan_deconv3d(N, Cin, Cout, D, H, W);
+  plan4[0] = p.form;
+  plan4[1] = p.CG;
+  plan4[2] = p.blocks_x;
+  plan4[3] = 0;
+  return PF_OK;
+}
 
 int pf_deconv3d_blocks(int64_t D, int64_t H, int64_t W) {
   if (D <= 0 || H <= 0 || W <= 0) return 0;
@@ -423,21 +464,12 @@ int pf_deconv3d_k3s2_f32(const float* xa, const float* xb, const float* w, float
     A.bn = *in_bn;
   }
   hipStream_t s = (hipStream_t)stream;
-  // The matrix-core form (whole channel quads, weights of 16 output channels within 64 KB of LDS) where it was measured
-  // faster (profiles/r06f_deconv_mfma.md): every block stages Cin * 27 * 16 weights, which only pays with >= 2 channel
-  // groups of 16 and a grid of >= 512 blocks -- config 4's data gradient of conv1_0 (16 -> 64 on 24x32x40: 35.6 us
-  // against 49.1); the decoder's 32 -> 16 and 16 -> 8 layers (30 / 240 blocks) stay on the lane-per-cell form (12.5 /
-  // 10.8 us against 17.8 / 18.7).  A shape always takes the same form, so results are reproducible run to run.
-  // PF_DECONV_MFMA=1 / PF_DECONV_VALU=1 force one form wherever it is valid (tests, tools/microbench_deconv3d.py).
-  const bool dm_ok = (Cin & 3) == 0 && Cin <= 32;
-  const bool dm_pays = Cout >= 32 && pf_cdiv(D * H * W, 128) * pf_cdiv(Cout, kDmCo) * N >= 512;
-  if (dm_ok && getenv("PF_DECONV_VALU") == nullptr && (dm_pays || getenv("PF_DECONV_MFMA") != nullptr))
+  const DcPlan plan = plan_deconv3d(N, Cin, Cout, D, H, W);
+  if (plan.form == 1)
     return launch_dm(xa, xb, w, y, N, (int)Cin, (int)Cout, (int)D, (int)H, (int)W, partials, A, s);
-  // channel group: 4 when that still leaves >= 2 blocks per CU, else 2 / 1 (more, smaller work items)
-  const int64_t cell_blocks = pf_cdiv(D * H * W, kDcThreads);
-  if ((Cout % 4) == 0 && cell_blocks * (Cout / 4) * N >= 512)
+  if (plan.CG == 4)
     return launch_dc<4>(xa, xb, w, y, N, (int)Cin, (int)Cout, (int)D, (int)H, (int)W, partials, A, s);
-  if ((Cout % 2) == 0 && cell_blocks * (Cout / 2) * N >= 512)
+  if (plan.CG == 2)
     return launch_dc<2>(xa, xb, w, y, N, (int)Cin, (int)Cout, (int)D, (int)H, (int)W, partials, A, s);
   return launch_dc<1>(xa, xb, w, y, N, (int)Cin, (int)Cout, (int)D, (int)H, (int)W, partials, A, s);
 }

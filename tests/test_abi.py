@@ -30,6 +30,32 @@ def test_header_library_and_bindings_agree(lib_built):
     assert lib.pf_stat_blocks(1, 100) == 2 and lib.pf_stat_blocks(0, 5) == 0
 
 
+def test_forward_plan_queries_report_the_arm_every_case_exists_for(lib_built, monkeypatch):
+    """pf_conv3d_plan / pf_deconv3d_plan are host-only and pure functions of the shape: every row of the forward-arm
+    tables (tests/conv_fwd_cases.py) reaches the tile depth, tiles per block, LDS size and deconvolution form it was
+    written for -- here already, before tests/test_gpu_conv_fwd_arms.py runs the rows on the device."""
+    import ctypes
+    import conv_fwd_cases as C
+    from pointmvsnet_amd import _lib
+    for case, want, _ in C.CONV_K3:
+        C.assert_conv_plan(case, want)
+    for case, want, _ in C.CONV_K3_TD1:
+        C.assert_conv_plan(case, want, ragged=False)
+    reached = {(C.conv_plan(c)["NT"], c[5], C.conv_plan(c)["TD"]) for c, _, _ in C.CONV_K3}
+    assert reached == {(2, 1, 4), (2, 1, 2), (1, 1, 2), (1, 2, 2), (2, 2, 2)}
+    for td in (4, 2):
+        assert any(w[1] == td and w[3] >= 2 for _, w, _ in C.CONV_K3)
+    assert any(w[5] > 65536 and w[3] >= 2 for _, w, _ in C.CONV_K3)
+    for case, want, _ in C.DECONV:
+        C.assert_deconv_plan(case, want, monkeypatch)
+    C.check_deconv_plan_honours_the_switches(monkeypatch)
+    plan = (ctypes.c_int * 8)()
+    lib = _lib.load()
+    assert lib.pf_conv3d_plan(6, 16, 4, 4, 4, 1, plan) == -2 and lib.pf_conv3d_plan(4, 33, 4, 4, 4, 1, plan) == -2
+    assert lib.pf_conv3d_plan(4, 16, 4, 4, 4, 3, plan) == -1 and lib.pf_conv3d_plan(4, 16, 4, 4, 4, 1, None) == -1
+    assert lib.pf_deconv3d_plan(1, 4, 4, 0, 4, 4, (ctypes.c_int * 4)()) == -1
+
+
 def test_library_contains_gfx950_code_object(lib_built):
     blob = open(lib_built, "rb").read()
     targets = set(re.findall(rb"amdgcn-amd-amdhsa--(gfx[0-9a-f]+)", blob))     # the offload bundles' code objects

@@ -8,6 +8,8 @@ are the GPU file's.
 No plan-feature assertions here: without a device the plan's occupancy comes from the fallback arithmetic
 (csrc/conv_wgrad.hip resident_blocks), which gives other splits and sometimes other tiles than the runtime's answer; the
 plan that ran goes to the parity report.  The cases are those that take a few seconds on the host.
+
+At the end: the cheapest rows of the forward-arm tables (tests/conv_fwd_cases.py) in the same manner.
 """
 import os
 import sys
@@ -83,6 +85,52 @@ def test_emulated_tower_data_gradient_at_small_and_odd_maps(cpu, case):
 def test_support_predicates_reject_single_value_batchnorm_sizes(cpu):
     """train_ops.volume_supported / tower_supported at (8, 8, 8) and (8, 8): False (the predicates look at shapes only)."""
     _C.check_predicates_reject_single_value_batchnorm(cpu)
+
+
+# ---------------------------------------------------------------------------------------------
+# The cheapest rows of the forward-arm tables (tests/conv_fwd_cases.py; all of them run on an MI355X in
+# tests/test_gpu_conv_fwd_arms.py), with the same checkers, plan assertions (those plans are pure functions of the shape)
+# and gates.  Left to the GPU: the 512-block TD-4 and stride-2 rows and the > 2048-tile rows (tens of seconds each here),
+# the matrix-core deconvolution by its shape rule (7 s), the GEMM and EdgeConv cases above their block caps, and the
+# 67 584-point lattices of knn_lattice_kernel<8> / <16>.
+# ---------------------------------------------------------------------------------------------
+import conv_fwd_cases as _F     # noqa: E402
+
+
+@pytest.mark.parametrize("case,want,why", _F.CONV_K3_TD1, ids=[_F.tag_of(c) for c, _, _ in _F.CONV_K3_TD1])
+def test_emulated_conv3d_k3_td1_twins(cpu, case, want, why):
+    _F.check_conv3d_plain(cpu, case, want, "emulated_arm_conv3d_td1", ragged=False)
+    for form in ("rows", "lazy"):
+        _F.check_conv3d_pending_batchnorm(cpu, case, want, form, "emulated_arm_conv3d_td1_bn", ragged=False)
+
+
+def test_emulated_conv3d_k3_td2_last_depth_tile_partial(cpu):
+    """The one deep-tile row that fits here: (4, 16, 7, 30, 250) stride 1, TD 2 on 512 blocks, 1 of 2 planes live in the
+    last depth tile."""
+    case, want, _ = _F.CONV_K3[4]
+    _F.check_conv3d_plain(cpu, case, want, "emulated_arm_conv3d")
+
+
+@pytest.mark.parametrize("case,want,why", _F.DECONV[:3], ids=[_F.tag_of(c) for c, _, _ in _F.DECONV[:3]])
+def test_emulated_deconv3d_channel_groups_picked_by_the_shape_rule(cpu, case, want, why, monkeypatch):
+    _F.check_deconv(cpu, case, want, True, monkeypatch, "emulated_arm_deconv3d")
+    if (case, want, why) in _F.DECONV_AFFINE:
+        for form in ("rows", "lazy"):
+            _F.check_deconv_pending_batchnorm(cpu, case, want, False, form, monkeypatch, "emulated_arm_deconv3d_bn")
+
+
+@pytest.mark.parametrize("case", _F.KNN_EMULATED, ids=[_F.knn_id(c) for c in _F.KNN_EMULATED])
+def test_emulated_knn_lattice_window_7(cpu, case):
+    _F.check_knn(cpu, *case)
+
+
+def test_emulated_knn_window_7_reports_unsupported_for_codes(cpu):
+    _F.check_knn_window7_has_no_codes(cpu)
+
+
+@pytest.mark.parametrize("k", [16, 5])
+def test_emulated_edgeconv_gather_passes_at_128_channels(cpu, k):
+    _F.check_edge_passes_c128(cpu, k, "emulated_arm_edgeconv")
 
 
 def test_composed_volume_path_raises_as_the_reference_does():
