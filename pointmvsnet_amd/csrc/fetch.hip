@@ -83,6 +83,20 @@ __device__ __forceinline__ float pf_variance(float s, float s2, float inv_v) {
   return fmaf(-m1, m1, s2 * inv_v);
 }
 
+// Tap addressing of the channel-last kernels (frustum_variance_cl_kernel, flow_features_hyp_kernel): a texel of a
+// (h*w, C) map is read as a UNIFORM 64-bit base (one view of one level) plus a 32-bit BYTE offset per lane, texel * 4C
+// by one 24-bit multiply, so a tap is a scalar-base load.  It holds for maps with h*w < 2^24 texels, 4C < 2^24 bytes per
+// texel and h*w*4C < 2^32 bytes per view (pf_tap_addressable; the entry points refuse larger maps).
+__device__ __forceinline__ unsigned pf_tap_byte_offset(int texel, unsigned texel_bytes) {
+  return ((unsigned)texel & 0xffffffu) * (texel_bytes & 0xffffffu);
+}
+__device__ __forceinline__ float4 pf_tap_load(const float* __restrict__ base, unsigned byte_off) {
+  return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(base) + byte_off);
+}
+inline bool pf_tap_addressable(int64_t texels, int64_t channels) {
+  return texels < (1ll << 24) && channels * 4 < (1ll << 24) && texels * channels * 4 < (1ll << 32);
+}
+
 // Frustum of the reference view (reference model.py:79-100): point n = d*H*W + y*W + x is the un-projection
 // of pixel centre (x+0.5, y+0.5) at depth hypothesis d,  world = Rinv (depth * Kinv (x+0.5, y+0.5, 1)^T - t).
 struct Frustum {
@@ -205,7 +219,12 @@ __global__ __launch_bounds__(256) void frustum_variance_cl_kernel(const float* _
                                                                   float* __restrict__ out, int C, int H, int W,
                                                                   int64_t N) {
   constexpr int PTS = 64;
+  constexpr int PV = V > 1 ? V - 1 : 1;                     // warped views (view 0 contributes its own texel)
+  constexpr int kPassUnroll = V <= 3 ? 2 : 1;               // two passes' loads in flight where the registers allow it
   __shared__ float tile[64 + 3][PTS + 1];
+  __shared__ int4 tap_boff[PV][PTS];                        // BYTE offsets of the four taps' texels (pf_tap_byte_offset)
+  __shared__ float4 tap_wgt[PV][PTS];
+  __shared__ unsigned ref_boff[PTS];                        // byte offset of the point's own texel in view 0
   const int q = threadIdx.x & 15, pl = threadIdx.x >> 4;
   const int64_t b = blockIdx.y;
   const int hw = H * W;
@@ -214,66 +233,96 @@ __global__ __launch_bounds__(256) void frustum_variance_cl_kernel(const float* _
   const float* ri = fr.rinv + b * 9;
   const float* tt = fr.t + b * 3;
   const float* mb = maps + b * V * (int64_t)hw * C;
+  const unsigned cb = (unsigned)C * 4u;                     // bytes per texel
+  // Prologue: every (point, warped view) pair of the block ONCE -- thread i takes point i % 64 and view 1 + i / 64 (the
+  // waves of a view share its camera) and parks byte offsets and weights in LDS.  Through round 6 each of the four
+  // passes of each 64-channel round recomputed the world position, the n -> (d, y, x) split and a projection on all 256
+  // lanes: ~420 vector instructions for 9 loads, the kernel ran at the vector-issue rate, not at a memory rate
+  // (profiles/r07_warp_valu_counters.md).
+  for (int i = threadIdx.x; i < PTS * PV; i += 256) {
+    const int p = i & (PTS - 1), vi = i / PTS;
+    int64_t n = n0 + p;
+    n = n < N ? n : N - 1;                                 // points past the end shadow the last point
+    const int d = (int)(n / hw);
+    const int pix = (int)(n - (int64_t)d * hw);
+    const int py = pix / W, px = pix - py * W;
+    const float gx = (float)px + 0.5f, gy = (float)py + 0.5f;
+    const float depth = fr.depths[b * fr.D + d];
+    const float u0 = fmaf(ki[2], 1.0f, fmaf(ki[1], gy, ki[0] * gx));
+    const float u1 = fmaf(ki[5], 1.0f, fmaf(ki[4], gy, ki[3] * gx));
+    const float u2 = fmaf(ki[8], 1.0f, fmaf(ki[7], gy, ki[6] * gx));
+    const float q0 = u0 * depth - tt[0], q1 = u1 * depth - tt[1], q2 = u2 * depth - tt[2];
+    const float X = fmaf(ri[2], q2, fmaf(ri[1], q1, ri[0] * q0));
+    const float Y = fmaf(ri[5], q2, fmaf(ri[4], q1, ri[3] * q0));
+    const float Z = fmaf(ri[8], q2, fmaf(ri[7], q1, ri[6] * q0));
+    if (vi == 0) {
+      tile[64][p] = X;
+      tile[65][p] = Y;
+      tile[66][p] = Z;
+      ref_boff[p] = pf_tap_byte_offset(pix, cb);
+    }
+    if (V > 1) {
+      const int v = 1 + vi;
+      PfTaps t;
+      pf_project_taps(X, Y, Z, Kmat + (b * V + v) * 9, Emat ? Emat + (b * V + v) * 12 : nullptr, H, W, t);
+      tap_boff[vi][p] = make_int4((int)pf_tap_byte_offset(t.off[0], cb), (int)pf_tap_byte_offset(t.off[1], cb),
+                                  (int)pf_tap_byte_offset(t.off[2], cb), (int)pf_tap_byte_offset(t.off[3], cb));
+      tap_wgt[vi][p] = make_float4(t.wgt[0], t.wgt[1], t.wgt[2], t.wgt[3]);
+    }
+  }
+  __syncthreads();
   for (int c0 = 0; c0 < C; c0 += 64) {
+    const int c = c0 + 4 * q;
+    const unsigned cq = (unsigned)c * 4u;
+    // a pass: 16 points x 16 channel quads.  kPassUnroll passes go together: their taps come from LDS, ALL their loads
+    // are issued, then each point is interpolated and accumulated as before (same calls, same view order)
 #pragma unroll 1
-    for (int pass = 0; pass < PTS / 16; ++pass) {
-      const int p = pass * 16 + pl;
-      int64_t n = n0 + p;
-      n = n < N ? n : N - 1;                               // lanes past the end shadow the last point
-      const int d = (int)(n / hw);
-      const int pix = (int)(n - (int64_t)d * hw);
-      const int py = pix / W, px = pix - py * W;
-      const float gx = (float)px + 0.5f, gy = (float)py + 0.5f;
-      const float depth = fr.depths[b * fr.D + d];
-      const float u0 = fmaf(ki[2], 1.0f, fmaf(ki[1], gy, ki[0] * gx));
-      const float u1 = fmaf(ki[5], 1.0f, fmaf(ki[4], gy, ki[3] * gx));
-      const float u2 = fmaf(ki[8], 1.0f, fmaf(ki[7], gy, ki[6] * gx));
-      const float q0 = u0 * depth - tt[0], q1 = u1 * depth - tt[1], q2 = u2 * depth - tt[2];
-      const float X = fmaf(ri[2], q2, fmaf(ri[1], q1, ri[0] * q0));
-      const float Y = fmaf(ri[5], q2, fmaf(ri[4], q1, ri[3] * q0));
-      const float Z = fmaf(ri[8], q2, fmaf(ri[7], q1, ri[6] * q0));
-      if (c0 == 0 && q < 3) tile[64 + q][p] = q == 0 ? X : (q == 1 ? Y : Z);
-      // the V - 1 projections of a point: lane q of its 16 lanes computes ONE of them (view 1 + q mod (V - 1)) and the
-      // 16 lanes exchange taps and weights by shuffles -- round 2 had every lane compute all V - 1 (~150 instructions
-      // each, two IEEE divisions: two thirds of the kernel's arithmetic at V = 3, 85 % at V = 7)
-      PfTaps t[V];
-      if (V > 1) {
-        const int vq = 1 + (q % (V > 1 ? V - 1 : 1));
-        PfTaps mine;
-        pf_project_taps(X, Y, Z, Kmat + (b * V + vq) * 9, Emat ? Emat + (b * V + vq) * 12 : nullptr, H, W, mine);
-#pragma unroll
-        for (int v = 1; v < V; ++v) {
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            t[v].off[k] = __shfl(mine.off[k], v - 1, 16);
-            t[v].wgt[k] = __shfl(mine.wgt[k], v - 1, 16);
-          }
-        }
-      }
-      const int c = c0 + 4 * q;
+    for (int pass0 = 0; pass0 < PTS / 16; pass0 += kPassUnroll) {
       if (c < C) {
-        // view 0 contributes its un-warped feature (model.py:103-106)
-        const float4 r0 = *reinterpret_cast<const float4*>(mb + (int64_t)pix * C + c);
-        float s[4] = {r0.x, r0.y, r0.z, r0.w};
-        float s2[4] = {r0.x * r0.x, r0.y * r0.y, r0.z * r0.z, r0.w * r0.w};
+        int4 o[kPassUnroll][PV];
+        float4 wg[kPassUnroll][PV], r0[kPassUnroll], tap[kPassUnroll][PV][4];
 #pragma unroll
-        for (int v = 1; v < V; ++v) {
-          const float* mv = mb + (int64_t)v * hw * C + c;
-          const float4 a = *reinterpret_cast<const float4*>(mv + (int64_t)t[v].off[0] * C);
-          const float4 bb = *reinterpret_cast<const float4*>(mv + (int64_t)t[v].off[1] * C);
-          const float4 cc = *reinterpret_cast<const float4*>(mv + (int64_t)t[v].off[2] * C);
-          const float4 dd = *reinterpret_cast<const float4*>(mv + (int64_t)t[v].off[3] * C);
-          const float w0 = t[v].wgt[0], w1 = t[v].wgt[1], w2 = t[v].wgt[2], w3 = t[v].wgt[3];
-          const float f[4] = {pf_bilerp(a.x, bb.x, cc.x, dd.x, w0, w1, w2, w3), pf_bilerp(a.y, bb.y, cc.y, dd.y, w0, w1, w2, w3),
-                              pf_bilerp(a.z, bb.z, cc.z, dd.z, w0, w1, w2, w3), pf_bilerp(a.w, bb.w, cc.w, dd.w, w0, w1, w2, w3)};
+        for (int u = 0; u < kPassUnroll; ++u) {
+          const int p = (pass0 + u) * 16 + pl;
+          // view 0 contributes its un-warped feature (model.py:103-106)
+          r0[u] = pf_tap_load(mb, ref_boff[p] + cq);
 #pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            s[i] = s[i] + f[i];
-            s2[i] = fmaf(f[i], f[i], s2[i]);
+          for (int v = 1; v < V; ++v) {
+            o[u][v - 1] = tap_boff[v - 1][p];
+            wg[u][v - 1] = tap_wgt[v - 1][p];
           }
         }
 #pragma unroll
-        for (int i = 0; i < 4; ++i) tile[4 * q + i][p] = pf_variance(s[i], s2[i], 1.0f / (float)V);
+        for (int u = 0; u < kPassUnroll; ++u) {
+#pragma unroll
+          for (int v = 1; v < V; ++v) {
+            const float* mv = mb + (int64_t)v * hw * C;        // uniform
+            tap[u][v - 1][0] = pf_tap_load(mv, (unsigned)o[u][v - 1].x + cq);
+            tap[u][v - 1][1] = pf_tap_load(mv, (unsigned)o[u][v - 1].y + cq);
+            tap[u][v - 1][2] = pf_tap_load(mv, (unsigned)o[u][v - 1].z + cq);
+            tap[u][v - 1][3] = pf_tap_load(mv, (unsigned)o[u][v - 1].w + cq);
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < kPassUnroll; ++u) {
+          const int p = (pass0 + u) * 16 + pl;
+          float s[4] = {r0[u].x, r0[u].y, r0[u].z, r0[u].w};
+          float s2[4] = {r0[u].x * r0[u].x, r0[u].y * r0[u].y, r0[u].z * r0[u].z, r0[u].w * r0[u].w};
+#pragma unroll
+          for (int v = 1; v < V; ++v) {
+            const float4 a = tap[u][v - 1][0], bb = tap[u][v - 1][1], cc = tap[u][v - 1][2], dd = tap[u][v - 1][3];
+            const float w0 = wg[u][v - 1].x, w1 = wg[u][v - 1].y, w2 = wg[u][v - 1].z, w3 = wg[u][v - 1].w;
+            const float f[4] = {pf_bilerp(a.x, bb.x, cc.x, dd.x, w0, w1, w2, w3), pf_bilerp(a.y, bb.y, cc.y, dd.y, w0, w1, w2, w3),
+                                pf_bilerp(a.z, bb.z, cc.z, dd.z, w0, w1, w2, w3), pf_bilerp(a.w, bb.w, cc.w, dd.w, w0, w1, w2, w3)};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              s[i] = s[i] + f[i];
+              s2[i] = fmaf(f[i], f[i], s2[i]);
+            }
+          }
+#pragma unroll
+          for (int i = 0; i < 4; ++i) tile[4 * q + i][p] = pf_variance(s[i], s2[i], 1.0f / (float)V);
+        }
       }
     }
     __syncthreads();
@@ -391,20 +440,29 @@ __global__ __launch_bounds__(256) void pyramid_resize_kernel(Pyramid py, int V, 
 // Output rows are POINT-major: feature (G*Ng, ctot), a point's ctot floats contiguous (the first
 // EdgeConv GEMM reads them as its A operand); xyz stays planar (G, 3, Ng) for the lattice kNN.
 constexpr int kFeatLanes = 8;
-constexpr int kFeatPY = 4, kFeatPX = 8;           // 32 points per 256-thread block
-static_assert(kFeatPY * kFeatPX * kFeatLanes == 256, "one point per 8 lanes");
+constexpr int kFeatPY = 2, kFeatPX = 8;           // 16 points per 256-thread block
+constexpr int kFeatGroups = 2;                    // two wave pairs per block: group g walks the 32-channel chunks k, k % 2 == g
+constexpr int kFeatThreads = kFeatPY * kFeatPX * kFeatLanes * kFeatGroups;
+static_assert(kFeatThreads <= 256 && (kFeatThreads / kFeatGroups) % PF_WAVE == 0, "a wave belongs to one group");
 
 // The five hypotheses of a pixel inside ONE block.  Round 1's kernel gave every hypothesis plane its own block; SQ / PMC
 // counters put it (and the coarse warp) at ~10 TB/s of L2 -> L1 tap traffic (550 MB of 128-byte tap lines per launch
 // at 4 x 25 600 points), not at HBM; it was removed in round 3 (59 vs 43 us at flow-2, outputs bit-identical).
 // The five hypotheses of a pixel are 0.1-0.3 texels apart in every source view, i.e. they sample the SAME four
-// texels almost always.  Here a block owns a 4 x 8 pixel patch with all five hypotheses and walks
+// texels almost always.  Here a block owns a 2 x 8 pixel patch with all five hypotheses and walks
 // level -> 32-channel chunk -> view -> hypothesis: within one (level, view) the five hypotheses re-read lines
-// that are in L1 already (6 x 10 texels x 64-256 B per view and level), which cuts the L2 traffic ~5x.  The
-// 15 (view, hypothesis) projections of a point are computed once by its 8 lanes (two each) and parked in LDS.
+// that are in L1 already (4 x 10 texels x 64-256 B per view and level), which cuts the L2 traffic ~5x.  The
+// 15 (view, hypothesis) projections of a point are computed once by its 16 lanes and parked in LDS.
 // Per (hypothesis, channel) the views are accumulated in ascending order.
+// Every pixel has its 8 lanes TWICE, in two wave pairs (groups) that deal the 32-channel chunks of the three levels
+// between them in turn.  The kernel waits on its taps, not on the vector pipe (42 % busy at flow-2, 18 % at flow-1,
+// every wave resident for the whole launch: profiles/r07_warp_valu_counters.md): through round 6 a wave of a 4 x 8 patch
+// walked all four chunks of the model's (16, 32, 64) pyramid one after the other, and 160 / 640 blocks left CUs empty
+// or unevenly filled.  Two groups halve that chain and double the blocks: 56.2 -> 45.1 us per depth map with the 32-bit
+// tap offsets (51.8 alone); four groups of one wave gain 2 us more at V = 3 and lose 10 % at V = 5 and 8
+// (profiles/r07_warp_kernel_times.md).
 template <int V, bool ROLLV>
-__global__ __launch_bounds__(256) void flow_features_hyp_kernel(const float* __restrict__ maps1,
+__global__ __launch_bounds__(kFeatThreads) void flow_features_hyp_kernel(const float* __restrict__ maps1,
                                                                 const float* __restrict__ maps2,
                                                                 const float* __restrict__ maps3, int c1, int c2,
                                                                 int c3, int h, int w,
@@ -412,7 +470,7 @@ __global__ __launch_bounds__(256) void flow_features_hyp_kernel(const float* __r
                                                                 const float* __restrict__ interval_p,
                                                                 const float* __restrict__ cam, int ratio,
                                                                 float* __restrict__ feature, float* __restrict__ xyz) {
-  constexpr int PTS = kFeatPY * kFeatPX;                    // 32 points (pixels) per block
+  constexpr int PTS = kFeatPY * kFeatPX;                    // 16 points (pixels) per block
   constexpr int kUnrollV = ROLLV ? 1 : V;                   // view loop: rolled (fewer registers) or unrolled
   __shared__ int tap_off[PTS][V * 5][4];
   __shared__ float tap_wgt[PTS][V * 5][4];
@@ -420,7 +478,8 @@ __global__ __launch_bounds__(256) void flow_features_hyp_kernel(const float* __r
   const int hs = h / ratio, ws = w / ratio;
   const int64_t Ng = (int64_t)5 * hs * ws;
   const int q = threadIdx.x & (kFeatLanes - 1);
-  const int pl = threadIdx.x / kFeatLanes;
+  const int grp = threadIdx.x / (PTS * kFeatLanes);         // uniform over a wave
+  const int pl = (threadIdx.x / kFeatLanes) % PTS;
   const int tiles_x = (w + kFeatPX - 1) / kFeatPX;
   const int bx = (int)blockIdx.x % tiles_x, by = (int)blockIdx.x / tiles_x;
   const int y_raw = by * kFeatPY + pl / kFeatPX, x_raw = bx * kFeatPX + pl % kFeatPX;
@@ -450,8 +509,8 @@ __global__ __launch_bounds__(256) void flow_features_hyp_kernel(const float* __r
     Y = fmaf(Ri[5], q2, fmaf(Ri[4], q1, Ri[3] * q0));
     Z = fmaf(Ri[8], q2, fmaf(Ri[7], q1, Ri[6] * q0));
   };
-  // phase 0: the V*5 (view, hypothesis) projections of this point, spread over its 8 lanes
-  for (int p = q; p < V * 5; p += kFeatLanes) {
+  // phase 0: the V*5 (view, hypothesis) projections of this point, spread over its 8 lanes in each group
+  for (int p = grp * kFeatLanes + q; p < V * 5; p += kFeatLanes * kFeatGroups) {
     const int v = p / 5, d = p - v * 5;
     float X, Y, Z;
     world(d, X, Y, Z);
@@ -464,7 +523,7 @@ __global__ __launch_bounds__(256) void flow_features_hyp_kernel(const float* __r
       tap_wgt[pl][p][k] = t.wgt[k];
     }
   }
-  if (q < 5) {
+  if (grp == 0 && q < 5) {
     float X, Y, Z;
     world(q, X, Y, Z);
     const float nx = (X - cam[PF_CAM_MEAN + 0]) / cam[PF_CAM_STD + 0];
@@ -486,15 +545,16 @@ __global__ __launch_bounds__(256) void flow_features_hyp_kernel(const float* __r
   float* frow0 = feature + ((int64_t)g * Ng + loc0) * ctot;       // + d*hs*ws*ctot per hypothesis
   const int64_t dstride = (int64_t)hs * ws * ctot;
   const int64_t hw = (int64_t)h * w;
-  int ch = 0;
+  int ch = 0, chunk = 0;
 #pragma unroll 1
   for (int level = 0; level < 3; ++level) {
     const float* maps = level == 0 ? maps1 : (level == 1 ? maps2 : maps3);
     const int cl = level == 0 ? c1 : (level == 1 ? c2 : c3);
 #pragma unroll 1
-    for (int c0 = 0; c0 < cl; c0 += 4 * kFeatLanes) {
+    for (int c0 = 0; c0 < cl; c0 += 4 * kFeatLanes, ++chunk) {
       const int c = c0 + 4 * q;
-      if (c < cl) {
+      if (chunk % kFeatGroups == grp && c < cl) {
+        const unsigned cb = (unsigned)cl * 4u, cq = (unsigned)c * 4u;   // bytes per texel, this lane's quad in it
         float s[5][4], s2[5][4];
         // (a zero start instead of "first view assigns" keeps every bit: 0 + f == f, and the sign of a zero sum
         // cannot reach m2 - m1 * m1)
@@ -504,15 +564,17 @@ __global__ __launch_bounds__(256) void flow_features_hyp_kernel(const float* __r
           for (int i = 0; i < 4; ++i) s[d][i] = s2[d][i] = 0.0f;
 #pragma unroll kUnrollV
         for (int v = 0; v < V; ++v) {
-          const float* mv = maps + (int64_t)v * hw * cl + c;
+          // the (level, view) base is uniform and 64-bit, the lane's part a 32-bit byte offset: one 24-bit multiply-add
+          // per tap where `mv + (int64_t)off * cl` cost about seven vector instructions, several at quarter rate
+          const float* mv = maps + (int64_t)v * hw * cl;
 #pragma unroll
           for (int d = 0; d < 5; ++d) {
             const int4 o = *reinterpret_cast<const int4*>(&tap_off[pl][v * 5 + d][0]);
             const float4 wg = *reinterpret_cast<const float4*>(&tap_wgt[pl][v * 5 + d][0]);
-            const float4 a = *reinterpret_cast<const float4*>(mv + (int64_t)o.x * cl);
-            const float4 b = *reinterpret_cast<const float4*>(mv + (int64_t)o.y * cl);
-            const float4 cc = *reinterpret_cast<const float4*>(mv + (int64_t)o.z * cl);
-            const float4 dd = *reinterpret_cast<const float4*>(mv + (int64_t)o.w * cl);
+            const float4 a = pf_tap_load(mv, pf_tap_byte_offset(o.x, cb) + cq);
+            const float4 b = pf_tap_load(mv, pf_tap_byte_offset(o.y, cb) + cq);
+            const float4 cc = pf_tap_load(mv, pf_tap_byte_offset(o.z, cb) + cq);
+            const float4 dd = pf_tap_load(mv, pf_tap_byte_offset(o.w, cb) + cq);
             const float f[4] = {pf_bilerp(a.x, b.x, cc.x, dd.x, wg.x, wg.y, wg.z, wg.w),
                                 pf_bilerp(a.y, b.y, cc.y, dd.y, wg.x, wg.y, wg.z, wg.w),
                                 pf_bilerp(a.z, b.z, cc.z, dd.z, wg.x, wg.y, wg.z, wg.w),
@@ -538,7 +600,7 @@ __global__ __launch_bounds__(256) void flow_features_hyp_kernel(const float* __r
     ch += cl;
   }
   // xyz.repeat(1, 8, 1): channel j of the 24 holds axis j % 3 (model.py:193-194); lanes 0..5 write 4 each
-  if (live && q < 6) {
+  if (grp == kFeatGroups - 1 && live && q < 6) {
 #pragma unroll
     for (int d = 0; d < 5; ++d) {
       float o[4];
@@ -711,10 +773,10 @@ int pf_frustum_variance_cl_f32(const float* maps_cl, const float* kinv, const fl
   PF_REQUIRE(B >= 0 && V >= 1 && C >= 0 && H >= 1 && W >= 1 && D >= 0);
   PF_REQUIRE(B <= 65535 && H * W <= INT32_MAX && C <= INT32_MAX && D <= INT32_MAX);
   if (V > PF_MAX_VIEWS || (C % 4) != 0) return PF_ERR_UNSUPPORTED;
+  if (!pf_tap_addressable(H * W, C)) return PF_ERR_UNSUPPORTED;       // 32-bit tap offsets (before anything is launched)
   const int64_t N = D * H * W;
   if (B == 0 || N == 0 || C == 0) return PF_OK;
   PF_REQUIRE(maps_cl && kinv && rinv && t && depths && K && out);
-  PF_REQUIRE(H * W * C <= (int64_t)INT32_MAX * 4);
   Frustum fr;
   fr.kinv = kinv;
   fr.rinv = rinv;
@@ -782,6 +844,9 @@ int pf_flow_features_f32(const float* maps1, const float* maps2, const float* ma
   PF_REQUIRE(h % ratio == 0 && w % ratio == 0);
   PF_REQUIRE(ratio * ratio <= 65535);
   if (V > PF_MAX_VIEWS) return PF_ERR_UNSUPPORTED;
+  // 32-bit tap offsets: every non-empty level must be addressable (before anything is launched)
+  for (const int cl : {c1, c2, c3})
+    if (cl > 0 && !pf_tap_addressable((int64_t)h * w, cl)) return PF_ERR_UNSUPPORTED;
   PF_REQUIRE(maps1 && maps2 && maps3 && depth_in && interval && cam && feature && xyz);
   const int64_t Ng = (int64_t)5 * (h / ratio) * (w / ratio);
   (void)Ng;
@@ -789,7 +854,7 @@ int pf_flow_features_f32(const float* maps1, const float* maps2, const float* ma
   dim3 gridh((unsigned)(pf_cdiv(h, kFeatPY) * pf_cdiv(w, kFeatPX)));
   return dispatch_views(V, [&](auto vtag) {
     constexpr int VV = decltype(vtag)::value;
-    hipLaunchKernelGGL((flow_features_hyp_kernel<VV, false>), gridh, dim3(256), 0, (hipStream_t)stream, maps1, maps2,
+    hipLaunchKernelGGL((flow_features_hyp_kernel<VV, false>), gridh, dim3(kFeatThreads), 0, (hipStream_t)stream, maps1, maps2,
                        maps3, c1, c2, c3, h, w, depth_in, dh, dw, interval, cam, ratio, feature, xyz);
     return pf_launch_status();
   });
