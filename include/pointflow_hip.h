@@ -724,6 +724,38 @@ int pf_tsdf_emit_triangles(const float* tsdf, const int* weight, int nx, int ny,
 int pf_tsdf_vertices_f32(const int64_t* keys, int64_t count, const float* tsdf, const unsigned char* colour, float ox, float oy,
                          float oz, float voxel, int nx, int ny, int nz, float* vertices, unsigned char* colours, void* stream);
 
+/* ---- mesh clean-up and scoring: components, vertex normals, surface samples (csrc/mesh_ops.hip) -----------------------
+ * The specification is this project's own (pointmvsnet_amd/mesh_ops.py).  vertices (Nv, 3) float32, faces (Nf, 3) int32,
+ * Nv, Nf <= PF_MESH_OPS_MAX.  Every kernel skips a face with an index outside [0, Nv); no argument can make one fault.
+ * pf_mesh_cc_hook: one hook launch of the hook-and-compress connected components on label (Nv) int32, which the caller
+ *   initialises to label[v] = v: per face, the roots of (a, b) and of (a, c) are united by atomicMin(label[larger root],
+ *   smaller); *changed is set to 1 iff some edge found two different roots (the caller zeroes it).
+ * pf_mesh_cc_compress: label[v] = the root of v's tree, for every v.  After a round (hook, compress) whose hook left
+ *   *changed at 0, label[v] is the smallest vertex index of v's connected component.
+ * pf_mesh_face_labels: face_label[f] = label[faces[f][0]], -1 for a skipped face.
+ * pf_mesh_vertex_normals_f32: offsets (Nv + 1) and corners (3 Nf) int64: vertex v owns the corners corners[offsets[v] ..
+ *   offsets[v + 1]), corner 3 f + j is faces[f][j], in ascending order.  Per corner's face (a, b, c): e1 = p_b - p_a,
+ *   e2 = p_c - p_a, n = e1 x e2 in float32 (each component a product, a product, a difference); skipped unless finite;
+ *   else added to a float64 sum in that order.  normals (Nv, 3) = (float)(s / len), len = sqrt((sx sx + sy sy) + sz sz) in
+ *   float64, (0, 0, 0) unless len is finite and positive.
+ * pf_mesh_sample_count_f32: count (Nf) int32 = floorf(x + u_f) clamped to 2^31 - 1, x = (0.5f * sqrtf((nx nx + ny ny) + nz nz))
+ *   * inv in float32 with n as above, u_f = (H(H(f ^ seed)) >> 8) * 2^-24, H = the hash of csrc/pf_hash.h; 0 unless x is finite.
+ * pf_mesh_sample_emit_f32: inclusive (Nf) int64 = the inclusive prefix sum of count, N its last value (<= PF_MESH_OPS_MAX).
+ *   Sample s belongs to the first face f with inclusive[f] > s, as its j-th (j = s - inclusive[f - 1]); i1 = H(H(f ^ seed) +
+ *   2 j + 1) >> 8, i2 likewise with 2 j + 2 (mod 2^32); if i1 + i2 > 2^24 both become 2^24 - i; r = i * 2^-24; bary (N, 3) =
+ *   ((2^24 - i1 - i2) * 2^-24, r1, r2); points (N, 3) = p_a + (r1 e1 + r2 e2) per coordinate in float32; face_index (N) = f.
+ *   A sample whose face cannot be found or is skipped gets zeros and face_index -1. */
+#define PF_MESH_OPS_MAX 2147483647LL
+int pf_mesh_cc_hook(const int* faces, int64_t Nf, int64_t Nv, int* label, int* changed, void* stream);
+int pf_mesh_cc_compress(int* label, int64_t Nv, void* stream);
+int pf_mesh_face_labels(const int* faces, int64_t Nf, int64_t Nv, const int* label, int* face_label, void* stream);
+int pf_mesh_vertex_normals_f32(const float* vertices, int64_t Nv, const int* faces, int64_t Nf, const int64_t* offsets,
+                               const int64_t* corners, float* normals, void* stream);
+int pf_mesh_sample_count_f32(const float* vertices, int64_t Nv, const int* faces, int64_t Nf, float inv, unsigned seed,
+                             int* count, void* stream);
+int pf_mesh_sample_emit_f32(const float* vertices, int64_t Nv, const int* faces, int64_t Nf, const int64_t* inclusive,
+                            int64_t N, unsigned seed, float* points, int* face_index, float* bary, void* stream);
+
 /* ---- image preprocessing from decoded uint8 views (csrc/preprocess.hip) -----------------------------------------
  * What reference dataset.py:269-287 does on the host before it uploads float32: cv2.resize, crop_dtu_input and
  * norm_image (utils/preprocess.py:6-11,56-85).  Specification: pointmvsnet_amd/utils/preprocess.py (the resize is this

@@ -132,6 +132,12 @@ PROTOTYPES = {
     "pf_tsdf_count_triangles": ([_vp, _vp, _i, _i, _i, _i, _vp, _vp], _i),
     "pf_tsdf_emit_triangles": ([_vp, _vp, _i, _i, _i, _i, _vp, _i64, _vp, _vp], _i),
     "pf_tsdf_vertices_f32": ([_vp, _i64, _vp, _vp, _f, _f, _f, _f, _i, _i, _i, _vp, _vp, _vp], _i),
+    "pf_mesh_cc_hook": ([_vp, _i64, _i64, _vp, _vp, _vp], _i),
+    "pf_mesh_cc_compress": ([_vp, _i64, _vp], _i),
+    "pf_mesh_face_labels": ([_vp, _i64, _i64, _vp, _vp, _vp], _i),
+    "pf_mesh_vertex_normals_f32": ([_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp], _i),
+    "pf_mesh_sample_count_f32": ([_vp, _i64, _vp, _i64, _f, ctypes.c_uint, _vp, _vp], _i),
+    "pf_mesh_sample_emit_f32": ([_vp, _i64, _vp, _i64, _vp, _i64, ctypes.c_uint, _vp, _vp, _vp, _vp], _i),
     "pf_preprocess_resize_u8": ([_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp], _i),
     "pf_preprocess_standardise_f32": ([_vp, _vp, _i, _i, _i, _vp, _vp], _i),
     "pf_scan_filter_supported": ([_i] * 7, _i),

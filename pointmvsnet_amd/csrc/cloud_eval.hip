@@ -28,17 +28,9 @@
 //   cloud_obs_mask / cloud_above_plane   the two DTU filters.
 // No float atomics, no LDS, no scratch; every load is guarded by the array length.  Two runs give identical bytes.
 #include "pf_cloud_grid.h"
+#include "pf_hash.h"
 
 namespace {
-
-__device__ __forceinline__ unsigned prio_hash(unsigned x) {
-  x ^= x >> 16;
-  x *= 0x7feb352du;
-  x ^= x >> 15;
-  x *= 0x846ca68bu;
-  x ^= x >> 16;
-  return x;
-}
 
 __global__ __launch_bounds__(256) void cloud_keys_kernel(const float* __restrict__ points, int64_t n, CloudGrid g,
                                                          int64_t* __restrict__ keys) {

@@ -40,7 +40,7 @@ so its results differ from this statement in the last bits; a zero weight times 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, mesh_ops
 from .cloud_filter import clean_cloud
 from .fusion import fuse_depth_maps
 from .geometric import geometric_filter
@@ -180,6 +180,7 @@ class ScanAccumulator(object):
         self._seen = [False] * self.view_num
         self._depth = self._flow = self._init = self._images = None
         self.last_clean_report = None
+        self.last_mesh_report = None
         self._with_image = 0
         self._K = np.zeros((self.view_num, 3, 3))
         self._E = np.zeros((self.view_num, 4, 4))
@@ -336,12 +337,20 @@ class ScanAccumulator(object):
         K, E = self.cameras()
         return render_mesh_depth_maps(vertices, faces, K, E, int(self._depth.shape[1]), int(self._depth.shape[2]), **kwargs)
 
-    def mesh(self, voxel, trunc=None, min_weight=2, bounds=None, filtered=True, with_colour=True):
+    def mesh(self, voxel, trunc=None, min_weight=2, bounds=None, filtered=True, with_colour=True,
+             min_component_faces=None, keep_largest=None, with_normals=False):
         """``(vertices (Nv, 3) float32, faces (Nf, 3) int32, colours (Nv, 3) uint8 or None)``: the accumulated depth maps --
         ``filtered()``, or the raw ``predictions()[0]`` with ``filtered=False`` -- integrated into a ``tsdf.TSDFVolume`` of
         pitch ``voxel`` and truncation ``trunc`` (default ``4 * voxel``) over the box ``bounds = (lo, hi)`` (default:
         ``tsdf.volume_bounds`` of the maps used, grown by ``trunc``), and its zero surface through the cells whose corners
-        were all seen by ``min_weight`` views (``tsdf.extract_mesh``).  Colours need the views' images."""
+        were all seen by ``min_weight`` views (``tsdf.extract_mesh``).  Colours need the views' images.
+
+        ``min_component_faces`` and ``keep_largest`` drop the mesh's small connected components
+        (``mesh_ops.remove_small_components``: ``min_faces``, ``keep_largest``); the report -- ``components``,
+        ``vertices_before`` / ``_after``, ``faces_before`` / ``_after``, ``rounds`` -- is kept as ``last_mesh_report`` (None
+        after a call with neither).  With ``with_normals`` a fourth value, the vertex normals (Nv, 3) float32 of the mesh
+        that is returned (``mesh_ops.vertex_normals``)."""
+        mesh_ops._check_selection("ScanAccumulator.mesh", min_component_faces, keep_largest)
         self._require_complete("mesh")
         voxel = float(voxel)
         trunc = 4.0 * voxel if trunc is None else float(trunc)
@@ -353,14 +362,30 @@ class ScanAccumulator(object):
         images = self.images() if with_colour else None
         volume = TSDFVolume(origin, voxel, dims, trunc, with_colour=images is not None, device=depths.device)
         volume.integrate(depths, K, E, images=images)
-        return volume.extract(min_weight)[:3]
+        vertices, faces, colours = volume.extract(min_weight)[:3]
+        self.last_mesh_report = None
+        if min_component_faces is not None or keep_largest is not None:
+            Nv, Nf = int(vertices.shape[0]), int(faces.shape[0])
+            faces32 = mesh_ops._faces32("ScanAccumulator.mesh", faces, Nv, vertices)
+            with _lib.on_device(faces32.device):
+                label, rounds = mesh_ops._components(faces32, Nv)
+                face_keep, components = mesh_ops._select_faces(mesh_ops._face_labels(faces32, Nv, label),
+                                                               min_component_faces, keep_largest)
+                vertices, faces, colours = mesh_ops._compact(vertices, faces, face_keep, colours, None)[:3]
+            self.last_mesh_report = {"components": components, "vertices_before": Nv, "vertices_after": int(vertices.shape[0]),
+                                     "faces_before": Nf, "faces_after": int(faces.shape[0]), "rounds": rounds}
+        if with_normals:
+            return vertices, faces, colours, mesh_ops.vertex_normals(vertices, faces)
+        return vertices, faces, colours
 
     def write_mesh(self, path, **mesh_kwargs):
-        """``mesh(**mesh_kwargs)`` written to ``path`` as a PLY with faces; returns what ``mesh`` returned."""
-        vertices, faces, colours = self.mesh(**mesh_kwargs)
+        """``mesh(**mesh_kwargs)`` written to ``path`` as a PLY with faces (and, ``with_normals``, the vertex normals); returns
+        what ``mesh`` returned."""
+        mesh = self.mesh(**mesh_kwargs)
+        vertices, faces, colours = mesh[:3]
         write_ply(path, vertices.cpu().numpy(), None if colours is None else colours.cpu().numpy(),
-                  faces=faces.cpu().numpy())
-        return vertices, faces, colours
+                  mesh[3].cpu().numpy() if len(mesh) > 3 else None, faces=faces.cpu().numpy())
+        return mesh
 
     def write_ply(self, path, **fuse_kwargs):
         """Fuse (``fuse_kwargs``: those of ``fuse``, ``method``, ``with_normals`` and ``clean`` among them) and write the cloud to

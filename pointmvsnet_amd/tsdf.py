@@ -78,7 +78,8 @@ Out of scope
 ------------
 Sparse or hashed volumes; per-axis voxel sizes; weighting by angle or confidence; de-integration; trilinear depth
 sampling; vertex normals from the TSDF gradient; mesh simplification or smoothing; Poisson reconstruction.  (Looking at
-the mesh from a camera is ``render.render_mesh_depth_maps``.)
+the mesh from a camera is ``render.render_mesh_depth_maps``; dropping its small components, area-weighted vertex normals
+and samples of its surface are ``mesh_ops.py``.)
 """
 import math
 

@@ -6,6 +6,7 @@ preprocessing, the network, the batched confidence filter, the fusion and, optio
         [--fusion roundtrip --num-src 10 --save-depth DIR] [--normals [--normal-step 2]] \
         [--voxel 0.2] [--outlier-radius 2.0 [--outlier-k 16] [--outlier-std 2.0] [--min-neighbors 4]] \
         [--mesh mesh.ply --mesh-voxel 0.5 [--mesh-trunc 2.0] [--mesh-min-weight 2] [--save-mesh-depth DIR]] \
+        [--mesh-min-component 100] [--mesh-keep-largest 1] [--mesh-normals] [--mesh-sample-pitch 0.2] \
         [--gt stl009_total.ply --obs-mask ObsMask9_10.mat --plane Plane9.mat [--depth-errors --splat 1]] \
         [--gt-mesh surface.ply --depth-errors]
 
@@ -31,6 +32,11 @@ with faces (pointmvsnet_amd/tsdf.py); the JSON line then carries ``mesh``: the g
 ``--gt``, ``evaluate_point_cloud`` of the mesh's vertices as ``score``, next to the cloud's.  ``--save-mesh-depth DIR`` also
 rasterises that mesh back into the scan's own views (``ScanAccumulator.render_mesh``) and writes every view's fused,
 hole-filled depth map as ``%08d_mesh.pfm``.
+``--mesh-min-component N`` and ``--mesh-keep-largest K`` drop the mesh's connected components of fewer than ``N`` faces and
+all but the ``K`` largest before it is written (pointmvsnet_amd/mesh_ops.py); ``mesh`` then carries the ``components``
+report.  ``--mesh-normals`` writes area-weighted vertex normals, ``nx ny nz``, next to the faces.  With ``--gt``, ``mesh``
+also gains ``score_sampled``: ``evaluate_point_cloud`` of ``sample_surface`` of the written mesh at ``--mesh-sample-pitch``
+(default: the evaluation's ``min_dist``), next to the unchanged ``score`` of its vertices, whose density is the voxel's.
 With ``--gt-mesh FILE`` (a PLY with faces) ``--depth-errors`` scores against the rasterised surface instead of the splatted
 cloud: no holes, and no back of the scene seen through a nearer surface; ``--splat`` is then not used.  The line's
 ``ground_truth`` names which of the two was used, ``"mesh"`` or ``"cloud"``.
@@ -98,6 +104,11 @@ def main():
     ap.add_argument("--mesh-trunc", type=float, default=None, help="--mesh: the truncation distance (default: 4 voxels)")
     ap.add_argument("--mesh-min-weight", type=int, default=2, help="--mesh: views that must have seen every corner of a cell")
     ap.add_argument("--save-mesh-depth", default=None, help="--mesh: folder for every view's depth map of the mesh, %%08d_mesh.pfm")
+    ap.add_argument("--mesh-min-component", type=int, default=None, help="--mesh: drop components of fewer faces")
+    ap.add_argument("--mesh-keep-largest", type=int, default=None, help="--mesh: keep only this many components, the largest")
+    ap.add_argument("--mesh-normals", action="store_true", help="--mesh: write area-weighted vertex normals")
+    ap.add_argument("--mesh-sample-pitch", type=float, default=None,
+                    help="--mesh with --gt: the pitch of the surface samples that are scored (default: the evaluation's min_dist)")
     ap.add_argument("--name", default="flow2")
     ap.add_argument("--num-view", type=int, default=5)
     ap.add_argument("--height", type=int, default=960)
@@ -172,9 +183,15 @@ def main():
         mesh_trunc = 4.0 * args.mesh_voxel if args.mesh_trunc is None else args.mesh_trunc
         K, E = acc.cameras()
         _, dims = tsdf.dims_for(tsdf.volume_bounds(filtered, K, E, pad=mesh_trunc), args.mesh_voxel)   # the grid mesh() builds
-        mesh_vertices, faces, _ = acc.write_mesh(args.mesh, **mesh_kwargs)
+        if args.mesh_min_component is not None or args.mesh_keep_largest is not None:
+            mesh_kwargs.update(min_component_faces=args.mesh_min_component, keep_largest=args.mesh_keep_largest)
+        if args.mesh_normals:
+            mesh_kwargs.update(with_normals=True)
+        mesh_vertices, faces = acc.write_mesh(args.mesh, **mesh_kwargs)[:2]
         out["mesh"] = {"out": args.mesh, "voxel": args.mesh_voxel, "trunc": mesh_trunc, "min_weight": args.mesh_min_weight,
                        "dims": list(dims), "vertices": int(mesh_vertices.shape[0]), "faces": int(faces.shape[0])}
+        if acc.last_mesh_report is not None:
+            out["mesh"]["components"] = acc.last_mesh_report
         print("mesh: grid %d x %d x %d, %d vertices, %d faces" % (tuple(dims) + (out["mesh"]["vertices"], out["mesh"]["faces"])),
               file=sys.stderr)
         if args.save_mesh_depth:
@@ -205,6 +222,15 @@ def main():
             out["score_before_cleaning"] = evaluation.evaluate_point_cloud(raw_points, gt, **kw)
         if mesh_vertices is not None and mesh_vertices.shape[0]:
             out["mesh"]["score"] = evaluation.evaluate_point_cloud(mesh_vertices, gt, **kw)
+            import inspect
+            from pointmvsnet_amd import mesh_ops
+            pitch = args.mesh_sample_pitch
+            if pitch is None:                                    # what evaluate_point_cloud thins at: no min_dist is passed above
+                pitch = kw.get("min_dist", inspect.signature(evaluation.evaluate_point_cloud).parameters["min_dist"].default)
+            samples = mesh_ops.sample_surface(mesh_vertices, faces, pitch)[0]
+            out["mesh"]["sample_pitch"], out["mesh"]["samples"] = float(pitch), int(samples.shape[0])
+            if samples.shape[0]:
+                out["mesh"]["score_sampled"] = evaluation.evaluate_point_cloud(samples, gt, **kw)
     print(json.dumps(out))
     if (args.gt or args.gt_mesh) and args.depth_errors:
         interval = float(dataset[0]["cam_params_list"][0, 1, 3, 1]) * INTERVAL_SCALE.get(args.name, 1.0)
