@@ -756,6 +756,42 @@ int pf_mesh_sample_count_f32(const float* vertices, int64_t Nv, const int* faces
 int pf_mesh_sample_emit_f32(const float* vertices, int64_t Nv, const int* faces, int64_t Nf, const int64_t* inclusive,
                             int64_t N, unsigned seed, float* points, int* face_index, float* bary, void* stream);
 
+/* ---- exact point-to-mesh distances (csrc/mesh_distance.hip) -----------------------------------------------------------
+ * The specification is this project's own (pointmvsnet_amd/mesh_distance.py): per query the lexicographic minimum of
+ * (d2, face index) over the faces, d2 the squared distance to the triangle in float64 from the float32 coordinates.  The
+ * search structure is the sorted sparse grid of the cloud kernels above with a (cell, face) pair for a point; ox .. nz are
+ * its origin, cell edge and cell counts (nx, ny, nz <= PF_CLOUD_MAX_CELLS).  vertices (Nv, 3) float32, faces (Nf, 3) int32,
+ * Nf <= PF_MESH_DIST_MAX_FACES.  A face with an index outside [0, Nv) or a non-finite vertex is skipped everywhere.
+ * pf_mesh_dist_count_f32: count (Nf) int64 = min(limit, the number of cells the face is listed in): the box from
+ *   cell(min - m) to cell(max + m) per axis over its vertices, cell(x) = floor((x - o) / edge) clamped to the grid, m =
+ *   PF_MESH_DIST_BOX_MARGIN * edge, all in float32; 0 for a skipped face.  1 <= limit <= 2^32.
+ * pf_mesh_dist_emit_f32: inclusive (Nf) int64 = the inclusive prefix sum of the UNCLAMPED counts, total its last value
+ *   (<= PF_MESH_DIST_MAX_PAIRS).  Pair s belongs to the first face f with inclusive[f] > s, as its j-th; its cell is the
+ *   j-th of the face's box, z fastest, then y.  keys (total) = cx << 42 | cy << 21 | cz, pair_face (total) = f.
+ * pf_mesh_dist_pack_f32: the caller sorts the keys; order (total) is that permutation.  records (total) 48-byte rows, 16-byte
+ *   aligned: (a.x, a.y, a.z, int32 face, b.x, b.y, b.z, 0, c.x, c.y, c.z, 0) of the face of pair order[i].
+ * pf_mesh_dist_cells_f64: one thread per query walks the cubes of radius 1, 3, .. rings (<= 15) cells around its cell;
+ *   done[i] = 1 and dist / face are final when the best distance is <= (r - 0.05) * edge or (r - 0.05) * edge >= max_dist;
+ *   done[i] = 0 otherwise and dist / face are not written.  d = (float)sqrt(d2); dist = max_dist and face = -1 unless
+ *   d < max_dist.
+ * pf_mesh_dist_wave_f64: one wave per query todo[0 .. ntodo) on a grid with edge >= max_dist: the 27 cells around it. */
+#define PF_MESH_DIST_MAX_FACES 134209536LL
+#define PF_MESH_DIST_MAX_PAIRS 2147483647LL
+#define PF_MESH_DIST_BOX_MARGIN 0.02f
+int pf_mesh_dist_count_f32(const float* vertices, int64_t Nv, const int* faces, int64_t Nf, float ox, float oy, float oz,
+                           float edge, int nx, int ny, int nz, int64_t limit, int64_t* count, void* stream);
+int pf_mesh_dist_emit_f32(const float* vertices, int64_t Nv, const int* faces, int64_t Nf, float ox, float oy, float oz,
+                          float edge, int nx, int ny, int nz, const int64_t* inclusive, int64_t total, int64_t* keys,
+                          int* pair_face, void* stream);
+int pf_mesh_dist_pack_f32(const float* vertices, int64_t Nv, const int* faces, int64_t Nf, const int* pair_face,
+                          const int64_t* order, int64_t total, void* records, void* stream);
+int pf_mesh_dist_cells_f64(const float* query, int64_t nq, const void* records, const int64_t* keys, int64_t total, float ox,
+                           float oy, float oz, float edge, int nx, int ny, int nz, int rings, float max_dist, float* dist,
+                           int* face, unsigned char* done, void* stream);
+int pf_mesh_dist_wave_f64(const float* query, const int64_t* todo, int64_t ntodo, int64_t nq, const void* records,
+                          const int64_t* keys, int64_t total, float ox, float oy, float oz, float edge, int nx, int ny, int nz,
+                          float max_dist, float* dist, int* face, void* stream);
+
 /* ---- image preprocessing from decoded uint8 views (csrc/preprocess.hip) -----------------------------------------
  * What reference dataset.py:269-287 does on the host before it uploads float32: cv2.resize, crop_dtu_input and
  * norm_image (utils/preprocess.py:6-11,56-85).  Specification: pointmvsnet_amd/utils/preprocess.py (the resize is this

@@ -138,6 +138,11 @@ PROTOTYPES = {
     "pf_mesh_vertex_normals_f32": ([_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp], _i),
     "pf_mesh_sample_count_f32": ([_vp, _i64, _vp, _i64, _f, ctypes.c_uint, _vp, _vp], _i),
     "pf_mesh_sample_emit_f32": ([_vp, _i64, _vp, _i64, _vp, _i64, ctypes.c_uint, _vp, _vp, _vp, _vp], _i),
+    "pf_mesh_dist_count_f32": ([_vp, _i64, _vp, _i64, _f, _f, _f, _f, _i, _i, _i, _i64, _vp, _vp], _i),
+    "pf_mesh_dist_emit_f32": ([_vp, _i64, _vp, _i64, _f, _f, _f, _f, _i, _i, _i, _vp, _i64, _vp, _vp, _vp], _i),
+    "pf_mesh_dist_pack_f32": ([_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp], _i),
+    "pf_mesh_dist_cells_f64": ([_vp, _i64, _vp, _vp, _i64, _f, _f, _f, _f, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp], _i),
+    "pf_mesh_dist_wave_f64": ([_vp, _vp, _i64, _i64, _vp, _vp, _i64, _f, _f, _f, _f, _i, _i, _i, _f, _vp, _vp, _vp], _i),
     "pf_preprocess_resize_u8": ([_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp], _i),
     "pf_preprocess_standardise_f32": ([_vp, _vp, _i, _i, _i, _vp, _vp], _i),
     "pf_scan_filter_supported": ([_i] * 7, _i),

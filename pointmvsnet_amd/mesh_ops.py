@@ -79,8 +79,8 @@ bary.view(1, 1, -1, 3), faces, attributes)``.
 Out of scope
 ------------
 Smoothing; simplification or decimation; hole filling; non-manifold repair; edge-connectivity (as opposed to
-vertex-connectivity) components; area thresholds for components; point-to-triangle distances; a wave-shared path for hub
-vertices.
+vertex-connectivity) components; area thresholds for components; a wave-shared path for hub vertices.  (Point-to-triangle
+distances are pointmvsnet_amd/mesh_distance.py.)
 """
 import math
 

@@ -40,6 +40,11 @@ also gains ``score_sampled``: ``evaluate_point_cloud`` of ``sample_surface`` of 
 With ``--gt-mesh FILE`` (a PLY with faces) ``--depth-errors`` scores against the rasterised surface instead of the splatted
 cloud: no holes, and no back of the scene seen through a nearer surface; ``--splat`` is then not used.  The line's
 ``ground_truth`` names which of the two was used, ``"mesh"`` or ``"cloud"``.
+With ``--mesh`` and ``--gt``, ``mesh`` also gains ``score_surface``: ``mesh_distance.evaluate_mesh`` of the written mesh, whose
+completeness is the exact distance from every ground-truth point to the surface (pointmvsnet_amd/mesh_distance.py) and
+whose accuracy uses the samples of ``score_sampled``; ``score`` and ``score_sampled`` are unchanged.  With ``--gt-mesh`` the first
+line gains ``score_gt_mesh``: ``evaluate_point_cloud_on_mesh`` of the written cloud against that surface (``--obs-mask`` and
+``--plane`` apply).
 """
 import argparse
 import json
@@ -231,6 +236,18 @@ def main():
             out["mesh"]["sample_pitch"], out["mesh"]["samples"] = float(pitch), int(samples.shape[0])
             if samples.shape[0]:
                 out["mesh"]["score_sampled"] = evaluation.evaluate_point_cloud(samples, gt, **kw)
+            from pointmvsnet_amd import mesh_distance
+            out["mesh"]["score_surface"] = mesh_distance.evaluate_mesh(mesh_vertices, faces, gt, pitch=pitch, **kw)
+    if args.gt_mesh and points.shape[0]:
+        from pointmvsnet_amd import mesh_distance
+        kw = {}
+        if args.obs_mask:
+            mask, bb_min, res = io.load_dtu_obs_mask(args.obs_mask)
+            kw.update(obs_mask=torch.from_numpy(mask), bb_min=bb_min, res=res)
+        if args.plane:
+            kw.update(plane=io.load_dtu_plane(args.plane))
+        surface_vertices, surface_faces = mesh_distance.load_ply_surface(args.gt_mesh, dev)
+        out["score_gt_mesh"] = mesh_distance.evaluate_point_cloud_on_mesh(points, surface_vertices, surface_faces, **kw)
     print(json.dumps(out))
     if (args.gt or args.gt_mesh) and args.depth_errors:
         interval = float(dataset[0]["cam_params_list"][0, 1, 3, 1]) * INTERVAL_SCALE.get(args.name, 1.0)
