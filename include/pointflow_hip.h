@@ -242,6 +242,11 @@ int pf_pointwise_gemm_f32(const float* X, int x_point_major, int64_t ldx, const 
 int pf_edge_stats_f32(const float* LE, int64_t ldle, int C, const int64_t* idx, int k, int G, int Ng,
                       double* partials, const uint8_t* codes, int lat_ks, int lat_h, int lat_w, void* stream);
 
+/* Both passes have a lean form for the launches the flow stage makes, with the address work of a point done once and
+ * shared by its lanes; it computes the same bits.  1 when a launch with these arguments takes it: window codes
+ * (has_codes != 0), k == 16, C in {32, 64}, ldle == 2C, and Ng * ldle * 4 < 2^32 (a group's rows are addressed with
+ * 32-bit byte offsets); 0 when it runs the general kernels. */
+int pf_edge_lean_supported(int C, int k, int64_t ldle, int Ng, int has_codes);
 
 /* Pass B of EdgeConv (reference networks.py:37-43 / :74-79):
  *   concat != 0: Y[m, 0:C]  = relu(l*scale[0:C] + shift[0:C])                       (central half)

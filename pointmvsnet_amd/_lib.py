@@ -92,6 +92,7 @@ PROTOTYPES = {
                                   _i64, _i64, _i64, _i, _d, _vp], _i),
     "pf_channel_bn_fused_f32": ([_vp, _vp, _i64, _i64, _i64, _i, _vp, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _i, _vp], _i),
     "pf_edge_stats_f32": ([_vp, _i64, _i, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp], _i),
+    "pf_edge_lean_supported": ([_i, _i, _i64, _i, _i], _i),
     "pf_edge_backward_sums_f32": ([_vp, _i64, _i, _vp, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp,
                                    _i64, _i, _vp], _i),
     "pf_edge_backward_finish_f32": ([_vp, _i64, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i,

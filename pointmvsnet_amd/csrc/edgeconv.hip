@@ -661,6 +661,223 @@ __global__ __launch_bounds__(256) void edge_apply_kernel(const float* __restrict
 }
 
 // ------------------------------------------------------------------------------------------------
+// The lean form of the two passes, for the route the flow stage takes (pf_edge_lean_supported: window codes, k = 16,
+// C = 32 | 64, ldle == 2C, a group's rows within 2^32 bytes).  Same loads, same float operations in the same order as
+// the kernels above -- the outputs are theirs bit for bit -- but the address work is done once per point instead of once
+// per lane:
+//   * the Q = C/4 lanes of a point deal its 16 codes (one each at C = 64, two at C = 32); a lane decodes its share
+//     (lut, clamp to the group) into the BYTE offset of the neighbour's row, i << log2(8C), and parks it in its wave's
+//     slot in LDS; every lane of the point reads the 16 offsets back as four 16-byte pieces.  A point's lanes sit in
+//     one wave, so a wave-level fence orders the exchange and no block barrier is needed;
+//   * a row load is the group's base (block-uniform, scalar registers) plus a 32-bit offset: one add per neighbour,
+//     no 64-bit arithmetic and no multiply (the tap addressing of fetch.hip);
+//   * tail points are clamped and their result dropped, so all lanes of a wave stay in the exchange;
+//   * the mean over the 16 neighbours is a multiplication by 1/16, exact like the division.
+// ------------------------------------------------------------------------------------------------
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+// Four waves per SIMD is what the 64 row registers of a point allow; said outright, so that the compiler does not trade
+// loads in flight for a register count that buys no fifth wave (it held back two of the 17 loads of a point otherwise).
+#if defined(__HIP_DEVICE_COMPILE__)
+#define PF_LEAN_WAVES __attribute__((amdgpu_waves_per_eu(4, 4)))
+#else
+#define PF_LEAN_WAVES
+#endif
+
+template <int C>
+struct LeanGeom {
+  static constexpr int Q = C / 4;            // lanes per point
+  static constexpr int PPB = 256 / Q;        // points per pass of the block
+  static constexpr int CPL = 16 / Q;         // codes a lane decodes: 1 (C = 64) or 2 (C = 32)
+  static constexpr int SH = C == 64 ? 9 : 8; // log2 of a row's bytes, 2C * 4
+  static_assert(C == 32 || C == 64, "lean form: C = 32 or 64");
+};
+
+// Orders one wave's LDS writes before its later LDS reads (and the other way round): a wave's LDS instructions execute
+// in order, so the fences cost no instruction; they keep the compiler from moving the accesses across the barrier.
+__device__ __forceinline__ void lean_wave_sync() {
+#if __has_builtin(__builtin_amdgcn_fence)
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#else
+  __builtin_amdgcn_wave_barrier();
+#endif
+}
+
+__device__ __forceinline__ float4 lean_ld4(const char* __restrict__ base, unsigned byte_off) {
+  return *reinterpret_cast<const float4*>(base + byte_off);
+}
+
+// This lane's share of the 16 codes of point nc (`cg`: the group's codes): one byte at C = 64, two at C = 32.
+template <int C>
+__device__ __forceinline__ unsigned lean_codes(const uint8_t* __restrict__ cg, int nc) {
+  typedef LeanGeom<C> L;
+  const unsigned cbyte = (unsigned)nc * 16u + (unsigned)((threadIdx.x % L::Q) * L::CPL);
+  if constexpr (L::CPL == 1) return cg[cbyte];
+  else return *reinterpret_cast<const uint16_t*>(cg + cbyte);
+}
+
+// Byte offsets of the 16 neighbour rows of point nc (already clamped to the group), relative to the group's first row.
+// `cw`: lean_codes of the point; `xch`: the block's exchange slots, 64 * CPL words per wave.
+template <int C>
+__device__ __forceinline__ void lean_offsets(unsigned cw, const int* lut, unsigned* xch, int nc, int Ng,
+                                             unsigned (&off)[16]) {
+  typedef LeanGeom<C> L;
+  const int tid = threadIdx.x;
+  lean_wave_sync();                          // the previous point's offsets have been read by all lanes
+#pragma unroll
+  for (int t = 0; t < L::CPL; ++t) {
+    const int code = (int)((cw >> (8 * t)) & 255u);
+    int i = nc + lut[code];
+    i = i < 0 ? 0 : (i > Ng - 1 ? Ng - 1 : i);
+    xch[tid * L::CPL + t] = (unsigned)i << L::SH;
+  }
+  lean_wave_sync();
+  const u32x4* sp = reinterpret_cast<const u32x4*>(xch + (tid / L::Q) * 16);
+#pragma unroll
+  for (int m = 0; m < 4; ++m) {
+    const u32x4 v = sp[m];
+    off[4 * m] = v.x; off[4 * m + 1] = v.y; off[4 * m + 2] = v.z; off[4 * m + 3] = v.w;
+  }
+}
+
+template <int C>
+__global__ __launch_bounds__(256) PF_LEAN_WAVES void edge_stats_lean_kernel(const float* __restrict__ LE, int Ng,
+                                                              double* __restrict__ partials, int T,
+                                                              const uint8_t* __restrict__ codes, Lattice lat) {
+  typedef LeanGeom<C> L;
+  constexpr int Q = L::Q, PPB = L::PPB;
+  __shared__ double red[256 * 8];
+  __shared__ int lut[256];
+  __shared__ __attribute__((aligned(16))) unsigned xch[256 * L::CPL];
+  build_code_lut(lut, lat);
+  const int tid = threadIdx.x;
+  const int q = tid % Q, pl = tid / Q;
+  const int g = blockIdx.y, tb = blockIdx.x;
+  const int tiles = (Ng + TILE - 1) / TILE;
+  const char* gb = reinterpret_cast<const char*>(LE + (int64_t)g * Ng * (2 * C));      // block-uniform
+  const uint8_t* cg = codes + (int64_t)g * Ng * 16;
+  const unsigned lpart = (unsigned)(C + 4 * q) * 4u;
+  double ds[4] = {0, 0, 0, 0}, dq[4] = {0, 0, 0, 0};
+  const int tile0 = xcd_tile(tb, lat);
+  for (int tile = tile0; tile < tiles; tile += T) {
+    const int n0 = tile * TILE;
+    unsigned cw = lean_codes<C>(cg, n0 + pl < Ng ? n0 + pl : Ng - 1);
+#pragma unroll 1
+    for (int p = pl; p < TILE; p += PPB) {
+      const int n = n0 + p;
+      const bool live = n < Ng;
+      const int nc = live ? n : Ng - 1;
+      const unsigned cw_next = lean_codes<C>(cg, n + PPB < Ng ? n + PPB : Ng - 1);   // in flight behind this point's rows
+      unsigned off[16];
+      lean_offsets<C>(cw, lut, xch, nc, Ng, off);
+      cw = cw_next;
+      const float4 l4 = lean_ld4(gb, ((unsigned)nc << L::SH) + 16u * (unsigned)q);
+      float4 e[16];
+#pragma unroll
+      for (int j = 0; j < 16; ++j) e[j] = lean_ld4(gb, off[j] + lpart);
+      const f32x2 l0 = {l4.x, l4.y}, l1 = {l4.z, l4.w};
+      f32x2 s0 = {0, 0}, s1 = {0, 0}, t0 = {0, 0}, t1 = {0, 0};
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const f32x2 e0 = {e[j].x, e[j].y}, e1 = {e[j].z, e[j].w};
+        const f32x2 d0 = e0 - l0, d1 = e1 - l1;
+        s0 += d0; s1 += d1;
+        t0 += d0 * d0; t1 += d1 * d1;
+      }
+      if (live) {
+        ds[0] += (double)s0.x; ds[1] += (double)s0.y; ds[2] += (double)s1.x; ds[3] += (double)s1.y;
+        dq[0] += (double)t0.x; dq[1] += (double)t0.y; dq[2] += (double)t1.x; dq[3] += (double)t1.y;
+      }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    red[tid * 8 + c] = ds[c];
+    red[tid * 8 + 4 + c] = dq[c];
+  }
+  __syncthreads();
+  if (tid < 2 * C) {
+    const int qq = tid / 8, comp = tid % 8;
+    double acc = 0.0;
+    for (int s = 0; s < PPB; ++s) acc += red[(s * Q + qq) * 8 + comp];
+    double* o = partials + (((int64_t)g * T + tile0) * C + 4 * qq + (comp & 3)) * 2 + (comp >> 2);
+    *o = acc;
+  }
+}
+
+template <int C>
+__global__ __launch_bounds__(256) PF_LEAN_WAVES void edge_apply_lean_kernel(const float* __restrict__ LE, int Ng,
+                                                              const float* __restrict__ scale,
+                                                              const float* __restrict__ shift, int ld_affine,
+                                                              int groups_per_stat, int concat, float* __restrict__ Y,
+                                                              int64_t ldy, int T, const uint8_t* __restrict__ codes,
+                                                              Lattice lat) {
+  typedef LeanGeom<C> L;
+  constexpr int Q = L::Q, PPB = L::PPB;
+  __shared__ int lut[256];
+  __shared__ __attribute__((aligned(16))) unsigned xch[256 * L::CPL];
+  build_code_lut(lut, lat);
+  const int tid = threadIdx.x;
+  const int q = tid % Q, pl = tid / Q;
+  const int g = blockIdx.y, tb = blockIdx.x;
+  const int tiles = (Ng + TILE - 1) / TILE;
+  const char* gb = reinterpret_cast<const char*>(LE + (int64_t)g * Ng * (2 * C));      // block-uniform
+  const uint8_t* cg = codes + (int64_t)g * Ng * 16;
+  float* yg = Y + (int64_t)g * Ng * ldy;
+  const unsigned lpart = (unsigned)(C + 4 * q) * 4u;
+  const int64_t so = (int64_t)(g / groups_per_stat) * ld_affine;
+  const int doff = concat ? C : 0;
+  const float4 dsc4 = ld4(scale + so + doff + 4 * q), dsh4 = ld4(shift + so + doff + 4 * q);
+  const f32x2 sc0 = {dsc4.x, dsc4.y}, sc1 = {dsc4.z, dsc4.w}, sh0 = {dsh4.x, dsh4.y}, sh1 = {dsh4.z, dsh4.w};
+  float4 csc = {0, 0, 0, 0}, csh = {0, 0, 0, 0};
+  if (concat) {
+    csc = ld4(scale + so + 4 * q);
+    csh = ld4(shift + so + 4 * q);
+  }
+  for (int tile = xcd_tile(tb, lat); tile < tiles; tile += T) {
+    const int n0 = tile * TILE;
+    unsigned cw = lean_codes<C>(cg, n0 + pl < Ng ? n0 + pl : Ng - 1);
+#pragma unroll 1
+    for (int p = pl; p < TILE; p += PPB) {
+      const int n = n0 + p;
+      const bool live = n < Ng;
+      const int nc = live ? n : Ng - 1;
+      const unsigned cw_next = lean_codes<C>(cg, n + PPB < Ng ? n + PPB : Ng - 1);   // in flight behind this point's rows
+      unsigned off[16];
+      lean_offsets<C>(cw, lut, xch, nc, Ng, off);
+      cw = cw_next;
+      const float4 l = lean_ld4(gb, ((unsigned)nc << L::SH) + 16u * (unsigned)q);
+      float4 e[16];
+#pragma unroll
+      for (int j = 0; j < 16; ++j) e[j] = lean_ld4(gb, off[j] + lpart);
+      const f32x2 l0 = {l.x, l.y}, l1 = {l.z, l.w};
+      f32x2 a0 = {0, 0}, a1 = {0, 0};
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const f32x2 e0 = {e[j].x, e[j].y}, e1 = {e[j].z, e[j].w};
+        const f32x2 u0 = __builtin_elementwise_fma(e0 - l0, sc0, sh0), u1 = __builtin_elementwise_fma(e1 - l1, sc1, sh1);
+        const f32x2 r0 = {fmaxf(u0.x, 0.0f), fmaxf(u0.y, 0.0f)}, r1 = {fmaxf(u1.x, 0.0f), fmaxf(u1.y, 0.0f)};
+        a0 += r0; a1 += r1;
+      }
+      a0 *= 0.0625f; a1 *= 0.0625f;          // mean over k = 16: exact, the bits of a / 16.0f
+      const float4 yd = {a0.x, a0.y, a1.x, a1.y};
+      if (live) {
+        float* yo = yg + (int64_t)n * ldy + 4 * q;
+        if (concat) {
+          float4 yc = {fmaxf(fmaf(l.x, csc.x, csh.x), 0.0f), fmaxf(fmaf(l.y, csc.y, csh.y), 0.0f),
+                       fmaxf(fmaf(l.z, csc.z, csh.z), 0.0f), fmaxf(fmaf(l.w, csc.w, csh.w), 0.0f)};
+          *reinterpret_cast<float4*>(yo) = yc;
+        }
+        *reinterpret_cast<float4*>(yo + doff) = yd;
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // EdgeConv backward (BASELINE config 4, training).  The reference differentiates the composition
 // conv1d / gather_knn / cat / BatchNorm2d / ReLU / mean (networks.py:18-45), which keeps the (B,2C,N,16)
 // edge tensor -- 839 MB at the 102 400-point lattice -- alive for backward and scatters through it with
@@ -1348,6 +1565,13 @@ static int xcd_band(int64_t plane, int unit, int64_t Ng, int64_t blocks) {      
 }
 static void lattice_band(Lattice& lat, int Ng, int T) { lat.band = xcd_band((int64_t)lat.H * lat.W, TILE, Ng, T); }
 
+// Whether a launch of the two gather passes takes their lean form (edge_*_lean_kernel): window codes, 16 neighbours,
+// rows of exactly [l | e] and a group whose rows a 32-bit byte offset reaches.  Everything else runs the general kernels.
+int pf_edge_lean_supported(int C, int k, int64_t ldle, int Ng, int has_codes) {
+  return has_codes != 0 && k == 16 && (C == 32 || C == 64) && ldle == 2 * (int64_t)C && Ng >= 1 &&
+         (int64_t)Ng * ldle * 4 < (1ll << 32);
+}
+
 int pf_edge_stats_f32(const float* LE, int64_t ldle, int C, const int64_t* idx, int k, int G, int Ng,
                       double* partials, const uint8_t* codes, int lat_ks, int lat_h, int lat_w, void* stream) {
   PF_REQUIRE(G >= 0 && Ng >= 0 && k >= 1 && ldle >= 2 * (int64_t)C && (ldle % 4) == 0 && G <= 65535);
@@ -1365,6 +1589,11 @@ int pf_edge_stats_f32(const float* LE, int64_t ldle, int C, const int64_t* idx, 
   lattice_band(lat, Ng, T);
   dim3 grid((unsigned)T, (unsigned)G);
   hipStream_t s = (hipStream_t)stream;
+  if (pf_edge_lean_supported(C, k, ldle, Ng, codes != nullptr)) {
+    if (C == 32) hipLaunchKernelGGL((edge_stats_lean_kernel<32>), grid, dim3(256), 0, s, LE, Ng, partials, T, codes, lat);
+    else hipLaunchKernelGGL((edge_stats_lean_kernel<64>), grid, dim3(256), 0, s, LE, Ng, partials, T, codes, lat);
+    return pf_launch_status();
+  }
 #define PF_ES(CV, KV) hipLaunchKernelGGL((edge_stats_kernel<CV, KV>), grid, dim3(256), 0, s, LE, ldle, idx, k, Ng, partials, T, status, codes, lat)
   if (k == 16) {
     if (C == 32) PF_ES(32, 16); else if (C == 64) PF_ES(64, 16); else PF_ES(128, 16);
@@ -1413,6 +1642,15 @@ int pf_edge_apply_f32(const float* LE, int64_t ldle, int C, const int64_t* idx, 
   lattice_band(lat, Ng, T);
   dim3 grid((unsigned)T, (unsigned)G);
   hipStream_t s = (hipStream_t)stream;
+  if (pf_edge_lean_supported(C, k, ldle, Ng, codes != nullptr)) {
+    if (C == 32)
+      hipLaunchKernelGGL((edge_apply_lean_kernel<32>), grid, dim3(256), 0, s, LE, Ng, scale, shift, ld_affine,
+                         groups_per_stat, concat, Y, ldy, T, codes, lat);
+    else
+      hipLaunchKernelGGL((edge_apply_lean_kernel<64>), grid, dim3(256), 0, s, LE, Ng, scale, shift, ld_affine,
+                         groups_per_stat, concat, Y, ldy, T, codes, lat);
+    return pf_launch_status();
+  }
 #define PF_EA(CV, KV)                                                                                         \
   hipLaunchKernelGGL((edge_apply_kernel<CV, KV>), grid, dim3(256), 0, s, LE, ldle, idx, k, Ng, scale, shift, \
                      ld_affine, groups_per_stat, concat, Y, ldy, T, codes, lat)

@@ -123,8 +123,8 @@ def model(cfg):
         (r"deconv3d_k3s2_kernel<", deconv),
         (r"conv3d_k3_few_kernel<", lambda a: (2.0 * 27 * 8 * vol, 4.0 * 9 * vol, "VolumeConv 8->1")),
         (r"pointwise_gemm_direct_kernel<", gemm),
-        (r"edge_stats_kernel<", edge(False)),
-        (r"edge_apply_kernel<", edge(True)),
+        (r"edge_stats(_lean)?_kernel<", edge(False)),
+        (r"edge_apply(_lean)?_kernel<", edge(True)),
         (r"frustum_variance_cl_kernel<", lambda a: (0.0, 4.0 * (V * 64 * FH * FW + 64 * vol + 3 * vol), "coarse warp + variance")),
         (r"flow_features_hyp_kernel<", lambda a: (0.0, sum(4.0 * (V * 112 * h * w + 139 * n + h * w) for n, h, w in its),
                                                   "flow feature assembly")),
