@@ -564,6 +564,28 @@ int pf_depth_normals_f32(const float* depth, const float* view_maps, int V, int 
 int pf_fuse_normals_f32(const float* normal_maps, const int* match, const unsigned char* emit, int V, int h, int w,
                         float* out, void* stream);
 
+/* ---- guided upsampling of depth maps by the views' images (csrc/depth_refine.hip) ----------------------------------
+ * A joint bilateral upsampler between the confidence filter and the fusers.  The specification is this project's own
+ * (pointmvsnet_amd/refine.py).  depth (V,h,w) float32, 0 = no depth; guide (V,H,W,3) uint8 with
+ * H = s h, W = s w, 1 <= s <= 8; pixel centres as above.
+ * pf_guide_pack_f32: records (V,h,w) of 8 bytes, per low-resolution pixel q: the bits of d(q), then r | g << 8 | b << 16 of
+ *   guide[qy s + s/2][qx s + s/2], the guide pixel that contains q's centre.
+ * pf_depth_upsample_f32: ws (s, 2 radius + 1) and wc (766) float32 as refine.spatial_table / refine.colour_table compose
+ *   them.  Per output pixel (X, Y) of view i, in float32 in this order, with c = (X / s, Y / s), (px, py) = (X % s, Y % s),
+ *   tap (tx, ty) the record q = c + (tx, ty) (a tap outside the map does not exist), valid(q) = depth_min < d(q) < depth_max,
+ *   a = the sum of the three absolute channel differences between q's colour and guide[Y][X], and
+ *   w(q) = (ws[py][ty + radius] * ws[px][tx + radius]) * wc[a]:
+ *   c not valid: out = 0, count = 0.  Else the anchor starts at c; over |tx|, |ty| <= anchor_radius in row-major order a
+ *   valid tap with a strictly larger w becomes the anchor; d0 = the anchor's depth.  linked(q) = valid(q) and
+ *   |d(q) - d0| <= rel_jump * d0.  Over |tx|, |ty| <= radius in row-major order, linked taps only: Wsum += w,
+ *   S += w * (d(q) - d0), count += 1.  out (V,H,W) = d0 + S / Wsum if Wsum > 0, else d0; count (V,H,W) int32, or NULL: not
+ *   written.  0 <= radius <= 8, 0 <= anchor_radius <= min(radius, 2), 0 <= rel_jump <= 0.5. */
+int pf_guide_pack_f32(const float* depth, const unsigned char* guide, int V, int h, int w, int s, void* records,
+                      void* stream);
+int pf_depth_upsample_f32(const void* records, const unsigned char* guide, const float* ws, const float* wc, int V, int h,
+                          int w, int s, int radius, int anchor_radius, float rel_jump, float depth_min, float depth_max,
+                          float* out, int* count, void* stream);
+
 /* ---- point-cloud evaluation: thinning and nearest distances between unordered clouds (csrc/cloud_eval.hip) -------
  * DTU's accuracy / completeness step, which the reference does not have (a separate MATLAB program).  The specification
  * is this project's own (pointmvsnet_amd/evaluation.py).  A cloud is searched through a sparse grid

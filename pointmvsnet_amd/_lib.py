@@ -112,6 +112,8 @@ PROTOTYPES = {
     "pf_geo_filter_f32": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _f, _f, _vp, _vp, _vp, _vp, _vp], _i),
     "pf_depth_normals_f32": ([_vp, _vp, _i, _i, _i, _i, _f, _f, _f, _vp, _vp], _i),
     "pf_fuse_normals_f32": ([_vp, _vp, _vp, _i, _i, _i, _vp, _vp], _i),
+    "pf_guide_pack_f32": ([_vp, _vp, _i, _i, _i, _i, _vp, _vp], _i),
+    "pf_depth_upsample_f32": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp], _i),
     "pf_cloud_cell_keys_f32": ([_vp, _i64, _f, _f, _f, _f, _i, _i, _i, _vp, _vp], _i),
     "pf_cloud_pack_f32": ([_vp, _vp, _i64, _i, _vp, _vp], _i),
     "pf_cloud_thin_round": ([_vp, _vp, _i64, _i, _i, _i, _f, _vp, _vp, _vp, _vp], _i),

@@ -90,11 +90,13 @@ int pf_eval_prob_filter_f32(const float* depth, const float* flow_conf, const fl
 // A build that is not hipcc's (no __HIP__: the host re-compilation of tests/hipemu, whose list of sources is fixed) gets
 // the next stage of the evaluation output, the fusion kernels, the scene input (preprocess.hip), the point-cloud
 // evaluation (cloud_eval.hip), the scan's confidence filter (scan_filter.hip), the round-trip consistency filter
-// (geo_filter.hip), the point-cloud renderer (cloud_render.hip), the normal maps (depth_normals.hip), the cloud cleaning
+// (geo_filter.hip), the point-cloud renderer (cloud_render.hip), the normal maps (depth_normals.hip), the guided depth
+// upsampling (depth_refine.hip), the cloud cleaning
 // (cloud_filter.hip), the meshing (tsdf.hip), the mesh rasteriser (mesh_render.hip), the mesh clean-up (mesh_ops.hip) and the
 // point-to-mesh distances (mesh_distance.hip) with this unit, so that such a library exports the whole C ABI.  hipcc
 // compiles fusion.hip, preprocess.hip, cloud_eval.hip, scan_filter.hip, geo_filter.hip, cloud_render.hip,
-// depth_normals.hip, cloud_filter.hip, tsdf.hip, mesh_render.hip, mesh_ops.hip and mesh_distance.hip as units of their own
+// depth_normals.hip, depth_refine.hip, cloud_filter.hip, tsdf.hip, mesh_render.hip, mesh_ops.hip and mesh_distance.hip as units of
+// their own
 // (build.SOURCES) and never takes this branch.
 #if !defined(__HIP__)
 #include "fusion.hip"
@@ -104,6 +106,7 @@ int pf_eval_prob_filter_f32(const float* depth, const float* flow_conf, const fl
 #include "geo_filter.hip"
 #include "cloud_render.hip"
 #include "depth_normals.hip"
+#include "depth_refine.hip"
 #include "cloud_filter.hip"
 #include "tsdf.hip"
 #include "mesh_render.hip"

@@ -45,6 +45,7 @@ from .cloud_filter import clean_cloud
 from .fusion import fuse_depth_maps
 from .geometric import geometric_filter
 from .normals import depth_normals
+from .refine import scale_of, upsample_depth_maps, upsampled_intrinsics
 from .render import depth_map_errors, render_depth_maps, render_mesh_depth_maps
 from .tsdf import TSDFVolume, dims_for, volume_bounds
 from .utils.eval_file_logger import _resize_nearest, _scene_paths
@@ -167,16 +168,20 @@ class ScanAccumulator(object):
     ``add(data_batch, preds)`` after every forward; then ``filtered()``, ``cameras()``, ``normals()``, ``fuse()``,
     ``write_ply(path)``, ``mesh(voxel)``, ``write_mesh(path, voxel=...)``.
     ``name`` is the depth map that is fused (``preds[name]``, ``preds[name + "_prob"]``), ``mode`` and the thresholds are
-    those of ``filter_depth_maps``; ``keep_images`` keeps the views' images for the cloud's colours."""
+    those of ``filter_depth_maps``; ``keep_images`` keeps the views' images for the cloud's colours; ``keep_guides`` also
+    keeps every view's full ``ref_img`` as RGB on the device, what ``upsampled()`` and ``fuse(upsample=...)`` are guided
+    by."""
 
     def __init__(self, view_num, name="flow2", mode="LANCZOS4", init_prob_threshold=0.2, flow_prob_threshold=0.1,
-                 keep_images=True):
+                 keep_images=True, keep_guides=False):
         _mode(mode)
         if int(view_num) < 1:
             raise ValueError("ScanAccumulator: view_num must be at least 1")
         self.view_num, self.name, self.mode = int(view_num), name, mode
         self.init_prob_threshold, self.flow_prob_threshold = float(init_prob_threshold), float(flow_prob_threshold)
-        self.keep_images = keep_images
+        self.keep_images, self.keep_guides = keep_images, bool(keep_guides)
+        self._guides = None
+        self._with_guide = 0
         self._seen = [False] * self.view_num
         self._depth = self._flow = self._init = self._images = None
         self.last_clean_report = None
@@ -226,6 +231,17 @@ class ScanAccumulator(object):
         ref_h = int(ref.shape[1]) if ref is not None else int(data_batch["img_list"].shape[3])
         cam[1, :2, :3] *= (float(h) / float(ref_h))            # cam_file of eval_file_logger_host, in the cameras' dtype
         self._K[v], self._E[v] = cam[1, :3, :3], cam[0]
+        if self.keep_guides and ref is not None:
+            full = torch.as_tensor(ref)[0]
+            if full.dim() != 3 or full.shape[2] != 3 or full.dtype != torch.uint8:
+                raise ValueError("ScanAccumulator: ref_img must be (1, H, W, 3) uint8")
+            if self._guides is None:
+                self._guides = torch.zeros((self.view_num,) + tuple(full.shape), dtype=torch.uint8, device=self._depth.device)
+            if tuple(full.shape) != tuple(self._guides.shape[1:]):
+                raise ValueError("ScanAccumulator: view %d's ref_img is %s, the first view's %s"
+                                 % (v, tuple(full.shape), tuple(self._guides.shape[1:])))
+            self._guides[v].copy_(full.flip(-1), non_blocking=True)          # BGR -> RGB, as the images below
+            self._with_guide += 1
         if self.keep_images and ref is not None:
             img = torch.as_tensor(ref)[0]
             if img.dim() != 3 or img.shape[2] != 3 or img.dtype != torch.uint8:
@@ -266,11 +282,32 @@ class ScanAccumulator(object):
         """(V, h, w, 3) uint8 RGB on the device, or None unless every view came with a ``ref_img``."""
         return self._images if self._with_image == self.view_num else None
 
-    def geometric(self, sources=None, **kwargs):
+    def guides(self):
+        """(V, H, W, 3) uint8 RGB on the device, the views' full ``ref_img``; None unless the accumulator was built with
+        ``keep_guides`` and every view came with a ``ref_img``."""
+        return self._guides if self._with_guide == self.view_num else None
+
+    def upsampled(self, **kwargs):
+        """``(depths_hi (V, H, W), K_hi (V, 3, 3), E (V, 4, 4), guides (V, H, W, 3))``: ``refine.upsample_depth_maps`` of
+        ``filtered()`` guided by the kept ``guides()`` (``kwargs``: its settings), with ``refine.upsampled_intrinsics`` of
+        ``cameras()``.  A ValueError without guides, or when ``H, W`` are not one integer multiple of ``h, w``."""
+        self._require_complete("upsampled")
+        guides = self.guides()
+        if guides is None:
+            raise ValueError("ScanAccumulator.upsampled: no guides were kept (keep_guides=True and a ref_img with every view)")
+        s = scale_of("ScanAccumulator.upsampled", self._depth.shape[1:], guides.shape[1:3])
+        K, E = self.cameras()
+        return upsample_depth_maps(self.filtered(), guides, **kwargs), upsampled_intrinsics(K, s), E, guides
+
+    def geometric(self, sources=None, upsample=None, **kwargs):
         """``geometric.geometric_filter`` of ``filtered()``, ``cameras()`` and ``images()``: ``(depth_avg, mask, count)`` and,
         unless ``return_points=False``, ``points`` and ``colours``.  ``sources``: the (V, M) table of source views (None: all
-        other views); ``kwargs``: its thresholds."""
+        other views); ``kwargs``: its thresholds.  ``upsample``: a dict of ``refine.upsample_depth_maps``' keyword arguments;
+        the filter then runs on ``upsampled()`` with the guides as the images."""
         self._require_complete("geometric")
+        if upsample is not None:
+            depths, K, E, guides = self.upsampled(**upsample)
+            return geometric_filter(depths, K, E, images=guides, sources=sources, **kwargs)
         K, E = self.cameras()
         return geometric_filter(self.filtered(), K, E, images=self.images(), sources=sources, **kwargs)
 
@@ -281,31 +318,41 @@ class ScanAccumulator(object):
         return depth_normals(self.filtered(), K, E, step=step, rel_jump=rel_jump)
 
     def fuse(self, disp_threshold=0.12, num_consistent=3, depth_min=1e-3, depth_max=1e5, method="disparity",
-             with_normals=False, normal_step=1, normal_rel_jump=0.01, clean=None, **kwargs):
+             with_normals=False, normal_step=1, normal_rel_jump=0.01, clean=None, upsample=None, **kwargs):
         """``(points (N, 3) float32, colours (N, 3) uint8 or None)``: with ``method="disparity"`` through
         ``fuse_depth_maps``; with ``method="roundtrip"`` the cloud of ``geometric()`` (``disp_threshold`` is not used;
         ``kwargs``: ``sources``, ``pix_threshold``, ``rel_depth_threshold``).  With ``with_normals`` a third value, the
         points' normals (N, 3) float32 as the method's fuser defines them (``normals.py``).  ``clean``: a dict of
         ``cloud_filter.clean_cloud``'s keyword arguments, applied to the cloud of either method with its colours and
         normals carried through; its report is kept as ``last_clean_report`` (None after a call without ``clean``).  ``None``
-        leaves the fuser's cloud as it is."""
+        leaves the fuser's cloud as it is.  ``upsample``: a dict of ``refine.upsample_depth_maps``' keyword arguments (an empty
+        one for its defaults); either method then fuses ``upsampled()`` -- the maps on the guides' grid with that grid's
+        intrinsics, colours taken from the guides -- and ``with_normals`` and ``clean`` act on that cloud.  It needs an
+        accumulator built with ``keep_guides``."""
         if method not in ("disparity", "roundtrip"):
             raise ValueError("ScanAccumulator.fuse: unknown method %r (disparity or roundtrip)" % (method,))
         if clean is not None and not isinstance(clean, dict):
             raise TypeError("ScanAccumulator.fuse: clean must be a dict of clean_cloud's keyword arguments or None")
+        if upsample is not None and not isinstance(upsample, dict):
+            raise TypeError("ScanAccumulator.fuse: upsample must be a dict of upsample_depth_maps' keyword arguments or None")
+        if upsample is not None and not self.keep_guides:
+            raise ValueError("ScanAccumulator.fuse: upsample needs an accumulator built with keep_guides=True")
         self._require_complete("fuse")
         normal_kwargs = {}
         if with_normals:
             normal_kwargs = {"with_normals": True, "normal_step": normal_step, "normal_rel_jump": normal_rel_jump}
         if method == "roundtrip":
             kwargs.update(normal_kwargs)
-            fused = self.geometric(num_consistent=num_consistent, depth_min=depth_min, depth_max=depth_max,
+            fused = self.geometric(num_consistent=num_consistent, depth_min=depth_min, depth_max=depth_max, upsample=upsample,
                                    **kwargs)[3:6 if with_normals else 5]
         else:
             if kwargs:
                 raise TypeError("ScanAccumulator.fuse: %s belong to method=\"roundtrip\"" % ", ".join(sorted(kwargs)))
-            K, E = self.cameras()
-            fused = fuse_depth_maps(self.filtered(), K, E, images=self.images(), disp_threshold=disp_threshold,
+            if upsample is not None:
+                depths, K, E, images = self.upsampled(**upsample)
+            else:
+                (K, E), depths, images = self.cameras(), self.filtered(), self.images()
+            fused = fuse_depth_maps(depths, K, E, images=images, disp_threshold=disp_threshold,
                                     num_consistent=num_consistent, depth_min=depth_min, depth_max=depth_max, **normal_kwargs)
         self.last_clean_report = None
         if clean is None:
@@ -400,7 +447,8 @@ def reconstruct_scan(model, batches, img_scales=(0.125, 0.25, 0.5), inter_scales
                      fuse_kwargs=None, **accumulator_kwargs):
     """Run ``model`` on every ``data_batch`` of one scan (any iterable; one view as the reference each), accumulate the
     views and fuse them: ``(points, colours, accumulator)``, or ``(points, colours, normals, accumulator)`` when
-    ``fuse_kwargs`` asks ``with_normals``.  A ``clean`` entry of ``fuse_kwargs`` cleans the cloud (``ScanAccumulator.fuse``).
+    ``fuse_kwargs`` asks ``with_normals``.  A ``clean`` entry of ``fuse_kwargs`` cleans the cloud (``ScanAccumulator.fuse``); an
+    ``upsample`` entry fuses the guided-upsampled maps and needs ``keep_guides=True`` among ``accumulator_kwargs``.
 
     A ``torch.nn.Module`` is called as the evaluation forward, ``model(data_batch, img_scales, inter_scales, isFlow=True,
     isTest=True)`` under ``torch.no_grad()``; anything else (a ``GraphedForward``) as ``model(data_batch)``.  ``view_num``

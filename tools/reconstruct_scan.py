@@ -8,7 +8,9 @@ preprocessing, the network, the batched confidence filter, the fusion and, optio
         [--mesh mesh.ply --mesh-voxel 0.5 [--mesh-trunc 2.0] [--mesh-min-weight 2] [--save-mesh-depth DIR]] \
         [--mesh-min-component 100] [--mesh-keep-largest 1] [--mesh-normals] [--mesh-sample-pitch 0.2] \
         [--gt stl009_total.ply --obs-mask ObsMask9_10.mat --plane Plane9.mat [--depth-errors --splat 1]] \
-        [--gt-mesh surface.ply --depth-errors]
+        [--gt-mesh surface.ply --depth-errors] \
+        [--upsample [--upsample-radius 2 --upsample-anchor-radius 1 --upsample-sigma-space 1.0 --upsample-sigma-colour 12.0
+                     --upsample-rel-jump 0.02]]
 
 ``--weights`` is a ``torch.load``-able file: its ``"model"`` entry if it has one, a leading ``module.`` stripped from the
 keys.  ``--fusion roundtrip`` replaces the disparity fusion by the round-trip consistency filter
@@ -45,6 +47,12 @@ completeness is the exact distance from every ground-truth point to the surface 
 whose accuracy uses the samples of ``score_sampled``; ``score`` and ``score_sampled`` are unchanged.  With ``--gt-mesh`` the first
 line gains ``score_gt_mesh``: ``evaluate_point_cloud_on_mesh`` of the written cloud against that surface (``--obs-mask`` and
 ``--plane`` apply).
+With ``--upsample`` the filtered depth maps are brought to the images' own grid before they are fused, guided by the images
+(pointmvsnet_amd/refine.py; the image size must be an integer multiple of the depth map's, at most 8): the cloud that is
+written, cleaned and scored is that of the upsampled maps, with colours from the full images.  The JSON line gains
+``upsample``: the scale, the settings, ``points_low_grid`` and ``points_high_grid`` -- the fuser's cloud on either grid, before
+any cleaning -- and, with ``--gt``, ``score_low_grid`` and ``score_high_grid`` of those two clouds.  ``--mesh``, ``--save-depth``
+and ``--depth-errors`` keep working on the depth maps' own grid.
 """
 import argparse
 import json
@@ -129,6 +137,12 @@ def main():
     ap.add_argument("--gt-mesh", default=None, help="the scan's ground-truth surface (PLY with faces) for --depth-errors")
     ap.add_argument("--depth-errors", action="store_true", help="with --gt or --gt-mesh: one more JSON line of per-view depth errors")
     ap.add_argument("--splat", type=int, default=1, help="--depth-errors: pixels around a projection that a point fills")
+    ap.add_argument("--upsample", action="store_true", help="fuse the depth maps upsampled to the images' grid, guided by the images")
+    ap.add_argument("--upsample-radius", type=int, default=2, help="--upsample: taps out to this many low-resolution pixels")
+    ap.add_argument("--upsample-anchor-radius", type=int, default=1, help="--upsample: the anchor's window (0: nearest replication's edges)")
+    ap.add_argument("--upsample-sigma-space", type=float, default=1.0, help="--upsample: in low-resolution pixels")
+    ap.add_argument("--upsample-sigma-colour", type=float, default=12.0, help="--upsample: in mean absolute channel difference")
+    ap.add_argument("--upsample-rel-jump", type=float, default=0.02, help="--upsample: relative depth jump that a tap may not bridge")
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args()
     if args.save_mesh_depth and not args.mesh:
@@ -156,9 +170,16 @@ def main():
         fuse_kwargs = dict(geo_kwargs, method="roundtrip")
     if args.normals:
         fuse_kwargs.update(with_normals=True, normal_step=args.normal_step)
+    low_grid_kwargs = dict(fuse_kwargs)
+    upsample = None
+    if args.upsample:
+        upsample = {"radius": args.upsample_radius, "anchor_radius": args.upsample_anchor_radius,
+                    "sigma_space": args.upsample_sigma_space, "sigma_colour": args.upsample_sigma_colour,
+                    "rel_jump": args.upsample_rel_jump}
+        fuse_kwargs["upsample"] = upsample
     points, colours, *normals, acc = scan.reconstruct_scan(
         net, batches_of(dataset, dev), tuple(args.img_scales), tuple(args.inter_scales), view_num=len(dataset),
-        fuse_kwargs=fuse_kwargs, name=args.name,
+        fuse_kwargs=fuse_kwargs, name=args.name, keep_guides=args.upsample,
         mode=args.mode, init_prob_threshold=args.init_prob_threshold, flow_prob_threshold=args.flow_prob_threshold)
     normals = normals[0] if normals else None
     clean = {}
@@ -177,6 +198,11 @@ def main():
     filtered, kept = acc.filtered(return_kept=True)
     out = {"scan": args.scan, "views": len(dataset), "mode": args.mode, "fusion": args.fusion, "points": int(points.shape[0]), "out": args.out,
            "kept_share_per_view": [k / float(filtered[0].numel()) for k in kept.cpu().tolist()]}
+    low_grid_points = None
+    if upsample is not None:
+        low_grid_points = acc.fuse(**low_grid_kwargs)[0]
+        out["upsample"] = dict(upsample, scale=int(acc.guides().shape[1]) // int(filtered.shape[1]),
+                               points_low_grid=int(low_grid_points.shape[0]), points_high_grid=int(raw_points.shape[0]))
     if clean:
         out["report"] = report
     if normals is not None:
@@ -225,6 +251,9 @@ def main():
         out["score"] = evaluation.evaluate_point_cloud(points, gt, **kw)
         if clean:
             out["score_before_cleaning"] = evaluation.evaluate_point_cloud(raw_points, gt, **kw)
+        if low_grid_points is not None:
+            out["upsample"]["score_low_grid"] = evaluation.evaluate_point_cloud(low_grid_points, gt, **kw)
+            out["upsample"]["score_high_grid"] = out["score_before_cleaning"] if clean else out["score"]
         if mesh_vertices is not None and mesh_vertices.shape[0]:
             out["mesh"]["score"] = evaluation.evaluate_point_cloud(mesh_vertices, gt, **kw)
             import inspect
