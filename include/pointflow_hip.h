@@ -586,6 +586,45 @@ int pf_depth_upsample_f32(const void* records, const unsigned char* guide, const
                           int w, int s, int radius, int anchor_radius, float rel_jump, float depth_min, float depth_max,
                           float* out, int* count, void* stream);
 
+/* ---- segments of depth maps: speckle removal and gap filling (csrc/depth_segments.hip) ------------------------------
+ * The specification is this project's own (pointmvsnet_amd/depth_segments.py).  depth (V,h,w) float32 with
+ * V h w <= PF_DEPTH_SEGMENTS_MAX; valid(q) = depth_min < d(q) < depth_max (0 <= depth_min < depth_max); two 4-neighbours
+ * p, q of one view are linked iff both are valid and |d(p) - d(q)| <= rel_jump * min(d(p), d(q)) in float32,
+ * 0 <= rel_jump <= 0.5.  A segment is a connected component of the link graph; its root is its first pixel in row-major
+ * order, as a flat index into (V,h,w).  n = V h w below.  No argument can make a kernel fault.
+ * pf_depth_tile_size: the tile of pf_depth_tile_segments_f32 (the library's compile-time choice).
+ * pf_depth_tile_segments_f32: label (V,h,w) int32 = the flat index of the root of the pixel's piece, the component of the
+ *   links INSIDE the pixel's tile (tiles start at multiples of the tile size in every view); -1 for a pixel that is not
+ *   valid.  piece (V,h,w) int32, or NULL: at a piece's root the number of its pixels, 0 elsewhere.
+ * pf_depth_border_merge_f32: one hook launch over the pixel edges that cross tile borders, on the label array above: the
+ *   roots of two linked pixels are united by atomicMin(label[larger root], smaller); *changed (the caller zeroes it) is
+ *   raised by the number of edges that found two different roots.
+ * pf_depth_label_compress: label[p] = the root of p's tree.  After a merge that left *changed at 0 -- on the labels as
+ *   pf_depth_tile_segments_f32 or the last compress left them -- label[p] is the root of p's segment.
+ * pf_depth_segment_sizes: size[label[p]] += piece[p] for every p (size (n) int32, zeroed by the caller): at a segment's
+ *   root, its number of pixels.
+ * pf_depth_speckle_mask_f32: s = size[label[p]] (0 for label -1); sizes (n) int32 = s; out (n) = d(p) if p is valid and
+ *   s >= min_size, else 0; removed (n) uint8 = p is valid and s < min_size.  Each of the three may be NULL: not written.
+ * pf_depth_gap_fill_f32: a valid pixel keeps its depth.  For a pixel (x, y) that is not valid the horizontal candidate
+ *   exists iff the nearest valid pixels xl < x < xr of its row exist, xr - xl - 1 <= max_gap and |dl - dr| <= (rel_jump *
+ *   float(xr - xl)) * min(dl, dr); its value is dl + (float(x - xl) / float(xr - xl)) * (dr - dl).  The vertical candidate
+ *   likewise along the column.  out = 0.5f * (dh + dv) if both exist, the one that exists, else 0; filled (V,h,w) uint8 (or
+ *   NULL) = a candidate exists.  All float32 in this order.  0 <= max_gap <= PF_DEPTH_GAP_MAX; out != depth. */
+#define PF_DEPTH_SEGMENTS_MAX 2147483647LL
+#define PF_DEPTH_GAP_MAX 32
+int pf_depth_tile_size(int* tile_w, int* tile_h);
+int pf_depth_tile_segments_f32(const float* depth, int V, int h, int w, float rel_jump, float depth_min, float depth_max,
+                               int* label, int* piece, void* stream);
+int pf_depth_border_merge_f32(const float* depth, int V, int h, int w, float rel_jump, float depth_min, float depth_max,
+                              int* label, int* changed, void* stream);
+int pf_depth_label_compress(int* label, int64_t n, void* stream);
+int pf_depth_segment_sizes(const int* label, const int* piece, int64_t n, int* size, void* stream);
+int pf_depth_speckle_mask_f32(const float* depth, const int* label, const int* size, int64_t n, int min_size,
+                              float depth_min, float depth_max, int* sizes, float* out, unsigned char* removed,
+                              void* stream);
+int pf_depth_gap_fill_f32(const float* depth, int V, int h, int w, int max_gap, float rel_jump, float depth_min,
+                          float depth_max, float* out, unsigned char* filled, void* stream);
+
 /* ---- point-cloud evaluation: thinning and nearest distances between unordered clouds (csrc/cloud_eval.hip) -------
  * DTU's accuracy / completeness step, which the reference does not have (a separate MATLAB program).  The specification
  * is this project's own (pointmvsnet_amd/evaluation.py).  A cloud is searched through a sparse grid

@@ -114,6 +114,13 @@ PROTOTYPES = {
     "pf_fuse_normals_f32": ([_vp, _vp, _vp, _i, _i, _i, _vp, _vp], _i),
     "pf_guide_pack_f32": ([_vp, _vp, _i, _i, _i, _i, _vp, _vp], _i),
     "pf_depth_upsample_f32": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp], _i),
+    "pf_depth_tile_size": ([ctypes.POINTER(_i), ctypes.POINTER(_i)], _i),
+    "pf_depth_tile_segments_f32": ([_vp, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp], _i),
+    "pf_depth_border_merge_f32": ([_vp, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp], _i),
+    "pf_depth_label_compress": ([_vp, _i64, _vp], _i),
+    "pf_depth_segment_sizes": ([_vp, _vp, _i64, _vp, _vp], _i),
+    "pf_depth_speckle_mask_f32": ([_vp, _vp, _vp, _i64, _i, _f, _f, _vp, _vp, _vp, _vp], _i),
+    "pf_depth_gap_fill_f32": ([_vp, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp], _i),
     "pf_cloud_cell_keys_f32": ([_vp, _i64, _f, _f, _f, _f, _i, _i, _i, _vp, _vp], _i),
     "pf_cloud_pack_f32": ([_vp, _vp, _i64, _i, _vp, _vp], _i),
     "pf_cloud_thin_round": ([_vp, _vp, _i64, _i, _i, _i, _f, _vp, _vp, _vp, _vp], _i),

@@ -46,8 +46,8 @@ Limits: ``0 <= radius <= 8``, ``0 <= anchor_radius <= min(radius, 2)``, ``0 <= r
 Cameras.  ``upsampled_intrinsics(K, s) = diag(s, s, 1) @ K``: with centres at ``(x + .5, y + .5)`` the centre of output
 pixel ``X`` is ``s`` times its position on the low-resolution grid, so this is exact.
 
-Out of scope: hole filling, upsampling of probabilities or normals, non-integer or anisotropic scales, ``mesh()`` on
-upsampled maps.
+Out of scope: hole filling (``depth_segments.fill_gaps`` closes small gaps before this stage), upsampling of probabilities
+or normals, non-integer or anisotropic scales, ``mesh()`` on upsampled maps.
 """
 import numpy as np
 import torch

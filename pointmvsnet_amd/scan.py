@@ -42,6 +42,7 @@ import torch
 
 from . import _lib, mesh_ops
 from .cloud_filter import clean_cloud
+from .depth_segments import check_clean_settings, clean_depth_maps
 from .fusion import fuse_depth_maps
 from .geometric import geometric_filter
 from .normals import depth_normals
@@ -170,13 +171,27 @@ class ScanAccumulator(object):
     ``name`` is the depth map that is fused (``preds[name]``, ``preds[name + "_prob"]``), ``mode`` and the thresholds are
     those of ``filter_depth_maps``; ``keep_images`` keeps the views' images for the cloud's colours; ``keep_guides`` also
     keeps every view's full ``ref_img`` as RGB on the device, what ``upsampled()`` and ``fuse(upsample=...)`` are guided
-    by."""
+    by.  ``clean_depth``: a dict of ``depth_segments.clean_depth_maps``' keyword arguments (an empty one for its defaults);
+    ``filtered()`` then returns the filtered maps with their speckles removed and their gaps filled, and everything that
+    consumes ``filtered()`` follows: ``fuse``, ``geometric``, ``normals``, ``upsampled``, ``mesh`` and
+    ``depth_errors(filtered=True)``.  The report of the latest cleaning is kept as ``last_depth_report``.  With ``None``
+    every method returns what it returned without the option."""
 
     def __init__(self, view_num, name="flow2", mode="LANCZOS4", init_prob_threshold=0.2, flow_prob_threshold=0.1,
-                 keep_images=True, keep_guides=False):
+                 keep_images=True, keep_guides=False, clean_depth=None):
         _mode(mode)
         if int(view_num) < 1:
             raise ValueError("ScanAccumulator: view_num must be at least 1")
+        if clean_depth is not None:
+            if not isinstance(clean_depth, dict):
+                raise ValueError("ScanAccumulator: clean_depth must be a dict of clean_depth_maps' keyword arguments or None")
+            try:
+                check_clean_settings("ScanAccumulator: clean_depth", **clean_depth)
+            except TypeError as exc:
+                raise ValueError("ScanAccumulator: clean_depth: %s" % exc)
+            clean_depth = dict(clean_depth)
+        self.clean_depth = clean_depth
+        self.last_depth_report = None
         self.view_num, self.name, self.mode = int(view_num), name, mode
         self.init_prob_threshold, self.flow_prob_threshold = float(init_prob_threshold), float(flow_prob_threshold)
         self.keep_images, self.keep_guides = keep_images, bool(keep_guides)
@@ -268,10 +283,15 @@ class ScanAccumulator(object):
         return self._depth, self._flow, self._init
 
     def filtered(self, return_kept=False):
-        """``filter_depth_maps`` of the accumulated views: (V, h, w)."""
+        """``filter_depth_maps`` of the accumulated views: (V, h, w); with ``clean_depth``, ``clean_depth_maps`` of that
+        (``kept`` stays the confidence filter's own count)."""
         self._require_complete("filtered")
-        return filter_depth_maps(self._depth, self._flow, self._init, self.init_prob_threshold, self.flow_prob_threshold,
-                                 self.mode, return_kept=return_kept)
+        out = filter_depth_maps(self._depth, self._flow, self._init, self.init_prob_threshold, self.flow_prob_threshold,
+                                self.mode, return_kept=return_kept)
+        if self.clean_depth is None:
+            return out
+        cleaned, self.last_depth_report = clean_depth_maps(out[0] if return_kept else out, **self.clean_depth)
+        return (cleaned, out[1]) if return_kept else cleaned
 
     def cameras(self):
         """``(intrinsics (V, 3, 3) of the depth maps' grid, extrinsics (V, 4, 4))`` as float64 NumPy."""

@@ -10,7 +10,8 @@ preprocessing, the network, the batched confidence filter, the fusion and, optio
         [--gt stl009_total.ply --obs-mask ObsMask9_10.mat --plane Plane9.mat [--depth-errors --splat 1]] \
         [--gt-mesh surface.ply --depth-errors] \
         [--upsample [--upsample-radius 2 --upsample-anchor-radius 1 --upsample-sigma-space 1.0 --upsample-sigma-colour 12.0
-                     --upsample-rel-jump 0.02]]
+                     --upsample-rel-jump 0.02]] \
+        [--speckle-size 100 --gap-size 7 [--segment-rel-jump 0.01]]
 
 ``--weights`` is a ``torch.load``-able file: its ``"model"`` entry if it has one, a leading ``module.`` stripped from the
 keys.  ``--fusion roundtrip`` replaces the disparity fusion by the round-trip consistency filter
@@ -53,6 +54,13 @@ written, cleaned and scored is that of the upsampled maps, with colours from the
 ``upsample``: the scale, the settings, ``points_low_grid`` and ``points_high_grid`` -- the fuser's cloud on either grid, before
 any cleaning -- and, with ``--gt``, ``score_low_grid`` and ``score_high_grid`` of those two clouds.  ``--mesh``, ``--save-depth``
 and ``--depth-errors`` keep working on the depth maps' own grid.
+With ``--speckle-size N`` and / or ``--gap-size G`` the filtered depth maps are cleaned on their own grid before anything
+consumes them (pointmvsnet_amd/depth_segments.py, ``clean_depth_maps``): segments of fewer than ``N`` pixels are removed, then
+gaps of at most ``G`` pixels are interpolated over; two neighbours belong to one segment when their depths differ by at most
+``--segment-rel-jump`` times the smaller.  The JSON line gains ``depth_cleaning``: the settings and the ``report`` of the
+cleaning; with ``--gt`` also ``score_without_depth_cleaning``, ``evaluate_point_cloud`` of the cloud that the same fusion (and
+cloud cleaning) gives without it; with ``--depth-errors`` the second line gains ``depth_errors_cleaned``, the errors of the
+cleaned maps, next to ``depth_errors_filtered``, which stays those of the confidence filter's maps.
 """
 import argparse
 import json
@@ -143,6 +151,10 @@ def main():
     ap.add_argument("--upsample-sigma-space", type=float, default=1.0, help="--upsample: in low-resolution pixels")
     ap.add_argument("--upsample-sigma-colour", type=float, default=12.0, help="--upsample: in mean absolute channel difference")
     ap.add_argument("--upsample-rel-jump", type=float, default=0.02, help="--upsample: relative depth jump that a tap may not bridge")
+    ap.add_argument("--speckle-size", type=int, default=None, help="remove depth-map segments of fewer pixels than this")
+    ap.add_argument("--gap-size", type=int, default=None, help="interpolate over depth-map gaps of at most this many pixels (<= 32)")
+    ap.add_argument("--segment-rel-jump", type=float, default=0.01,
+                    help="--speckle-size, --gap-size: neighbours are linked up to this relative depth difference")
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args()
     if args.save_mesh_depth and not args.mesh:
@@ -177,9 +189,12 @@ def main():
                     "sigma_space": args.upsample_sigma_space, "sigma_colour": args.upsample_sigma_colour,
                     "rel_jump": args.upsample_rel_jump}
         fuse_kwargs["upsample"] = upsample
+    clean_depth = None
+    if args.speckle_size is not None or args.gap_size is not None:
+        clean_depth = {"min_size": args.speckle_size or 0, "max_gap": args.gap_size or 0, "rel_jump": args.segment_rel_jump}
     points, colours, *normals, acc = scan.reconstruct_scan(
         net, batches_of(dataset, dev), tuple(args.img_scales), tuple(args.inter_scales), view_num=len(dataset),
-        fuse_kwargs=fuse_kwargs, name=args.name, keep_guides=args.upsample,
+        fuse_kwargs=fuse_kwargs, name=args.name, keep_guides=args.upsample, clean_depth=clean_depth,
         mode=args.mode, init_prob_threshold=args.init_prob_threshold, flow_prob_threshold=args.flow_prob_threshold)
     normals = normals[0] if normals else None
     clean = {}
@@ -198,6 +213,8 @@ def main():
     filtered, kept = acc.filtered(return_kept=True)
     out = {"scan": args.scan, "views": len(dataset), "mode": args.mode, "fusion": args.fusion, "points": int(points.shape[0]), "out": args.out,
            "kept_share_per_view": [k / float(filtered[0].numel()) for k in kept.cpu().tolist()]}
+    if clean_depth is not None:
+        out["depth_cleaning"] = dict(clean_depth, report=acc.last_depth_report)
     low_grid_points = None
     if upsample is not None:
         low_grid_points = acc.fuse(**low_grid_kwargs)[0]
@@ -251,6 +268,13 @@ def main():
         out["score"] = evaluation.evaluate_point_cloud(points, gt, **kw)
         if clean:
             out["score_before_cleaning"] = evaluation.evaluate_point_cloud(raw_points, gt, **kw)
+        if clean_depth is not None:                          # the same fusion and cloud cleaning of the maps as the filter left them
+            acc.clean_depth = None
+            uncleaned = acc.fuse(**fuse_kwargs)
+            acc.clean_depth = clean_depth
+            if clean:
+                uncleaned = cloud_filter.clean_cloud(uncleaned[0], uncleaned[1], None, **clean)
+            out["score_without_depth_cleaning"] = evaluation.evaluate_point_cloud(uncleaned[0], gt, **kw)
         if low_grid_points is not None:
             out["upsample"]["score_low_grid"] = evaluation.evaluate_point_cloud(low_grid_points, gt, **kw)
             out["upsample"]["score_high_grid"] = out["score_before_cleaning"] if clean else out["score"]
@@ -294,7 +318,11 @@ def main():
             kw = {"splat": args.splat}
             line.update(ground_truth="cloud", splat=args.splat)
         line["depth_errors_raw"] = acc.depth_errors(gt, thresholds, filtered=False, **kw)
+        acc.clean_depth = None
         line["depth_errors_filtered"] = acc.depth_errors(gt, thresholds, filtered=True, **kw)
+        if clean_depth is not None:
+            acc.clean_depth = clean_depth
+            line["depth_errors_cleaned"] = acc.depth_errors(gt, thresholds, filtered=True, **kw)
         print(json.dumps(line))
 
 
