@@ -625,6 +625,33 @@ int pf_depth_speckle_mask_f32(const float* depth, const int* label, const int* s
 int pf_depth_gap_fill_f32(const float* depth, int V, int h, int w, int max_gap, float rel_jump, float depth_min,
                           float depth_max, float* out, unsigned char* filled, void* stream);
 
+/* ---- photometric consistency of depth maps: windowed ZNCC (csrc/photo_filter.hip) -----------------------------------
+ * The one check of the chain that looks at the images again.  The specification is this project's own
+ * (pointmvsnet_amd/photometric.py).  Maps, pixel centres, `sources` and `pair_maps` as for
+ * pf_geo_filter_f32 (only entry [i][m][0], the i -> j row, is read).  All float32 operations in the stated order.
+ * pf_grey_pack_u8: rgb (n, 3) uint8 -> grey (n) uint8, g = (77 R + 150 G + 29 B + 128) >> 8.
+ * pf_grey_quads_u8: grey (V,h,w) uint8 -> quads (V,h,w) uint32, g(y, x) | g(y, x + 1) << 8 | g(y + 1, x) << 16 |
+ *   g(y + 1, x + 1) << 24, a neighbour beyond the last column or row repeating the last one: the four bytes of a bilinear tap
+ *   in one load.  g_i below is the low byte.
+ * pf_photo_ncc_f32: quads (V,h,w) uint32 as above; 1 <= radius = r <= 5, n = (2 r + 1)^2, var_min >= 1.  Per pixel p = (x, y) of view
+ *   i with d = d_i(p), c = g_i(p): over the taps (dx, dy) in [-r, r]^2, R = g_i(y + dy, x + dx) - c, SR = sum R,
+ *   SRR = sum R^2, VR = n SRR - SR^2 (int32, exact).  p is scorable iff depth_min < d < depth_max, r <= x < w - r,
+ *   r <= y < h - r and VR >= var_min.  Per listed source j (dy ascending outside, dx ascending inside):
+ *   (qx, qy, z) = (M_ij (x + dx + .5, y + dy + .5, 1)) d + T_ij, rz = 1 / z, (u, v) = (qx rz, qy rz), (fx, fy) = (u - .5,
+ *   v - .5), (x0, y0) = floor(fx, fy); the tap is inside iff z > 0, 0 <= x0, x0 + 1 <= w - 1, 0 <= y0, y0 + 1 <= h - 1;
+ *   s = (top (1 - wy) + bot wy) - float(c) with top = t00 (1 - wx) + t01 wx, bot = t10 (1 - wx) + t11 wx over g_j as float;
+ *   S1 += s, S2 += s s, SX += float(R) s.  VS = n S2 - S1 S1, COV = n SX - float(SR) S1.  j is usable iff p is scorable, every
+ *   tap is inside and VS >= float(var_min); its ncc = fminf(1, fmaxf(-1, COV / sqrtf(float(VR) VS))).
+ *   ncc (V,M,h,w), or NULL: the usable sources' ncc, a quiet NaN elsewhere (pads and i itself included).  usable (V,h,w)
+ *   int32 = usable sources; count (V,h,w) int32 = those with ncc >= ncc_threshold; score (V,h,w) = the sum of the usable ncc
+ *   in slot order / float(usable), 0 without one; mask (V,h,w) uint8: bit 0 = p is scorable and count >= num_consistent,
+ *   bit 1 = p is scorable. */
+int pf_grey_pack_u8(const unsigned char* rgb, int64_t n, unsigned char* grey, void* stream);
+int pf_grey_quads_u8(const unsigned char* grey, int V, int h, int w, unsigned* quads, void* stream);
+int pf_photo_ncc_f32(const float* depth, const unsigned* quads, const int* sources, const float* pair_maps, int V, int M,
+                     int h, int w, int radius, int var_min, float ncc_threshold, int num_consistent, float depth_min,
+                     float depth_max, float* ncc, float* score, int* count, int* usable, unsigned char* mask, void* stream);
+
 /* ---- point-cloud evaluation: thinning and nearest distances between unordered clouds (csrc/cloud_eval.hip) -------
  * DTU's accuracy / completeness step, which the reference does not have (a separate MATLAB program).  The specification
  * is this project's own (pointmvsnet_amd/evaluation.py).  A cloud is searched through a sparse grid

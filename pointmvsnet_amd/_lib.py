@@ -121,6 +121,9 @@ PROTOTYPES = {
     "pf_depth_segment_sizes": ([_vp, _vp, _i64, _vp, _vp], _i),
     "pf_depth_speckle_mask_f32": ([_vp, _vp, _vp, _i64, _i, _f, _f, _vp, _vp, _vp, _vp], _i),
     "pf_depth_gap_fill_f32": ([_vp, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp], _i),
+    "pf_grey_pack_u8": ([_vp, _i64, _vp, _vp], _i),
+    "pf_grey_quads_u8": ([_vp, _i, _i, _i, _vp, _vp], _i),
+    "pf_photo_ncc_f32": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp], _i),
     "pf_cloud_cell_keys_f32": ([_vp, _i64, _f, _f, _f, _f, _i, _i, _i, _vp, _vp], _i),
     "pf_cloud_pack_f32": ([_vp, _vp, _i64, _i, _vp, _vp], _i),
     "pf_cloud_thin_round": ([_vp, _vp, _i64, _i, _i, _i, _f, _vp, _vp, _vp, _vp], _i),

@@ -46,6 +46,7 @@ from .depth_segments import check_clean_settings, clean_depth_maps
 from .fusion import fuse_depth_maps
 from .geometric import geometric_filter
 from .normals import depth_normals
+from .photometric import photometric_consistency, photometric_filter
 from .refine import scale_of, upsample_depth_maps, upsampled_intrinsics
 from .render import depth_map_errors, render_depth_maps, render_mesh_depth_maps
 from .tsdf import TSDFVolume, dims_for, volume_bounds
@@ -175,7 +176,9 @@ class ScanAccumulator(object):
     ``filtered()`` then returns the filtered maps with their speckles removed and their gaps filled, and everything that
     consumes ``filtered()`` follows: ``fuse``, ``geometric``, ``normals``, ``upsampled``, ``mesh`` and
     ``depth_errors(filtered=True)``.  The report of the latest cleaning is kept as ``last_depth_report``.  With ``None``
-    every method returns what it returned without the option."""
+    every method returns what it returned without the option.  ``photometric()`` scores the maps against the kept images
+    (``photometric.py``), and ``fuse(photo={...})`` removes what fails that check before fusing; the report of the latest such
+    call is kept as ``last_photo_report``."""
 
     def __init__(self, view_num, name="flow2", mode="LANCZOS4", init_prob_threshold=0.2, flow_prob_threshold=0.1,
                  keep_images=True, keep_guides=False, clean_depth=None):
@@ -200,6 +203,7 @@ class ScanAccumulator(object):
         self._seen = [False] * self.view_num
         self._depth = self._flow = self._init = self._images = None
         self.last_clean_report = None
+        self.last_photo_report = None
         self.last_mesh_report = None
         self._with_image = 0
         self._K = np.zeros((self.view_num, 3, 3))
@@ -331,6 +335,22 @@ class ScanAccumulator(object):
         K, E = self.cameras()
         return geometric_filter(self.filtered(), K, E, images=self.images(), sources=sources, **kwargs)
 
+    def photometric(self, sources=None, upsample=None, **kwargs):
+        """``photometric.photometric_consistency`` of ``filtered()``, ``cameras()`` and ``images()``: ``(score, mask, count,
+        usable)`` and, with ``return_per_source``, ``ncc``.  ``sources``: the (V, M) table of source views (None: all other
+        views); ``kwargs``: its settings.  ``images()`` are the views' images nearest-resized to the depth maps' grid, so
+        the windows compare subsampled images; ``upsample``: a dict of ``refine.upsample_depth_maps``' keyword arguments, with
+        which the check runs on ``upsampled()`` with the guides as the images -- the images as they were taken, the honest
+        resolution for a photometric test.  A ValueError without images."""
+        self._require_complete("photometric")
+        if upsample is not None:
+            depths, K, E, images = self.upsampled(**upsample)
+        else:
+            (K, E), depths, images = self.cameras(), self.filtered(), self.images()
+        if images is None:
+            raise ValueError("ScanAccumulator.photometric: no images were kept (keep_images=True and a ref_img with every view)")
+        return photometric_consistency(depths, images, K, E, sources=sources, **kwargs)
+
     def normals(self, step=1, rel_jump=0.01):
         """``normals.depth_normals`` of ``filtered()`` and ``cameras()``: (V, h, w, 3) unit normals facing their camera."""
         self._require_complete("normals")
@@ -338,7 +358,7 @@ class ScanAccumulator(object):
         return depth_normals(self.filtered(), K, E, step=step, rel_jump=rel_jump)
 
     def fuse(self, disp_threshold=0.12, num_consistent=3, depth_min=1e-3, depth_max=1e5, method="disparity",
-             with_normals=False, normal_step=1, normal_rel_jump=0.01, clean=None, upsample=None, **kwargs):
+             with_normals=False, normal_step=1, normal_rel_jump=0.01, clean=None, upsample=None, photo=None, **kwargs):
         """``(points (N, 3) float32, colours (N, 3) uint8 or None)``: with ``method="disparity"`` through
         ``fuse_depth_maps``; with ``method="roundtrip"`` the cloud of ``geometric()`` (``disp_threshold`` is not used;
         ``kwargs``: ``sources``, ``pix_threshold``, ``rel_depth_threshold``).  With ``with_normals`` a third value, the
@@ -348,30 +368,41 @@ class ScanAccumulator(object):
         leaves the fuser's cloud as it is.  ``upsample``: a dict of ``refine.upsample_depth_maps``' keyword arguments (an empty
         one for its defaults); either method then fuses ``upsampled()`` -- the maps on the guides' grid with that grid's
         intrinsics, colours taken from the guides -- and ``with_normals`` and ``clean`` act on that cloud.  It needs an
-        accumulator built with ``keep_guides``."""
+        accumulator built with ``keep_guides``.  ``photo``: a dict of ``photometric.photometric_filter``'s keyword arguments
+        (``sources`` among them; an empty one for its defaults); the maps -- the upsampled ones under ``upsample``, with the
+        guides as their images -- then pass that filter before either method's fuser, and its report is kept as
+        ``last_photo_report`` (None after a call without ``photo``).  It needs the views' images."""
         if method not in ("disparity", "roundtrip"):
             raise ValueError("ScanAccumulator.fuse: unknown method %r (disparity or roundtrip)" % (method,))
         if clean is not None and not isinstance(clean, dict):
             raise TypeError("ScanAccumulator.fuse: clean must be a dict of clean_cloud's keyword arguments or None")
         if upsample is not None and not isinstance(upsample, dict):
             raise TypeError("ScanAccumulator.fuse: upsample must be a dict of upsample_depth_maps' keyword arguments or None")
+        if photo is not None and not isinstance(photo, dict):
+            raise TypeError("ScanAccumulator.fuse: photo must be a dict of photometric_filter's keyword arguments or None")
         if upsample is not None and not self.keep_guides:
             raise ValueError("ScanAccumulator.fuse: upsample needs an accumulator built with keep_guides=True")
         self._require_complete("fuse")
         normal_kwargs = {}
         if with_normals:
             normal_kwargs = {"with_normals": True, "normal_step": normal_step, "normal_rel_jump": normal_rel_jump}
+        if method == "disparity" and kwargs:
+            raise TypeError("ScanAccumulator.fuse: %s belong to method=\"roundtrip\"" % ", ".join(sorted(kwargs)))
+        if upsample is not None:
+            depths, K, E, images = self.upsampled(**upsample)
+        else:
+            (K, E), depths, images = self.cameras(), self.filtered(), self.images()
+        self.last_photo_report = None
+        if photo is not None:
+            if images is None:
+                raise ValueError("ScanAccumulator.fuse: photo needs the views' images (keep_images=True and a ref_img with "
+                                 "every view)")
+            depths, self.last_photo_report = photometric_filter(depths, images, K, E, **photo)
         if method == "roundtrip":
             kwargs.update(normal_kwargs)
-            fused = self.geometric(num_consistent=num_consistent, depth_min=depth_min, depth_max=depth_max, upsample=upsample,
-                                   **kwargs)[3:6 if with_normals else 5]
+            fused = geometric_filter(depths, K, E, images=images, num_consistent=num_consistent, depth_min=depth_min,
+                                     depth_max=depth_max, **kwargs)[3:6 if with_normals else 5]
         else:
-            if kwargs:
-                raise TypeError("ScanAccumulator.fuse: %s belong to method=\"roundtrip\"" % ", ".join(sorted(kwargs)))
-            if upsample is not None:
-                depths, K, E, images = self.upsampled(**upsample)
-            else:
-                (K, E), depths, images = self.cameras(), self.filtered(), self.images()
             fused = fuse_depth_maps(depths, K, E, images=images, disp_threshold=disp_threshold,
                                     num_consistent=num_consistent, depth_min=depth_min, depth_max=depth_max, **normal_kwargs)
         self.last_clean_report = None
@@ -468,7 +499,8 @@ def reconstruct_scan(model, batches, img_scales=(0.125, 0.25, 0.5), inter_scales
     """Run ``model`` on every ``data_batch`` of one scan (any iterable; one view as the reference each), accumulate the
     views and fuse them: ``(points, colours, accumulator)``, or ``(points, colours, normals, accumulator)`` when
     ``fuse_kwargs`` asks ``with_normals``.  A ``clean`` entry of ``fuse_kwargs`` cleans the cloud (``ScanAccumulator.fuse``); an
-    ``upsample`` entry fuses the guided-upsampled maps and needs ``keep_guides=True`` among ``accumulator_kwargs``.
+    ``upsample`` entry fuses the guided-upsampled maps and needs ``keep_guides=True`` among ``accumulator_kwargs``; a
+    ``photo`` entry passes the maps through ``photometric.photometric_filter`` first.
 
     A ``torch.nn.Module`` is called as the evaluation forward, ``model(data_batch, img_scales, inter_scales, isFlow=True,
     isTest=True)`` under ``torch.no_grad()``; anything else (a ``GraphedForward``) as ``model(data_batch)``.  ``view_num``

@@ -9,6 +9,7 @@ preprocessing, the network, the batched confidence filter, the fusion and, optio
         [--mesh-min-component 100] [--mesh-keep-largest 1] [--mesh-normals] [--mesh-sample-pitch 0.2] \
         [--gt stl009_total.ply --obs-mask ObsMask9_10.mat --plane Plane9.mat [--depth-errors --splat 1]] \
         [--gt-mesh surface.ply --depth-errors] \
+        [--photo-ncc 0.6 [--photo-radius 2 --photo-min-consistent 2 --photo-min-variance 25]] \
         [--upsample [--upsample-radius 2 --upsample-anchor-radius 1 --upsample-sigma-space 1.0 --upsample-sigma-colour 12.0
                      --upsample-rel-jump 0.02]] \
         [--speckle-size 100 --gap-size 7 [--segment-rel-jump 0.01]]
@@ -61,6 +62,13 @@ gaps of at most ``G`` pixels are interpolated over; two neighbours belong to one
 cleaning; with ``--gt`` also ``score_without_depth_cleaning``, ``evaluate_point_cloud`` of the cloud that the same fusion (and
 cloud cleaning) gives without it; with ``--depth-errors`` the second line gains ``depth_errors_cleaned``, the errors of the
 cleaned maps, next to ``depth_errors_filtered``, which stays those of the confidence filter's maps.
+With ``--photo-ncc T`` the maps that are fused -- the upsampled ones under ``--upsample``, with the full images -- first pass the
+photometric check (pointmvsnet_amd/photometric.py, ``photometric_filter``): a pixel stays when the windowed ZNCC of its
+``2 R + 1`` window (``--photo-radius R``) reaches ``T`` in at least ``--photo-min-consistent`` of its ``--num-src`` source
+views from ``pair.txt``; windows below ``--photo-min-variance`` are not scored and go.  The JSON line gains ``photometric``:
+the settings and the filter's ``report`` (valid, scorable, kept and removed pixels per view and in total, also printed); with
+``--gt`` also ``score_without_photometric``, ``evaluate_point_cloud`` of the cloud that the same fusion (and cloud cleaning)
+gives without the check, next to ``score``.
 """
 import argparse
 import json
@@ -155,6 +163,12 @@ def main():
     ap.add_argument("--gap-size", type=int, default=None, help="interpolate over depth-map gaps of at most this many pixels (<= 32)")
     ap.add_argument("--segment-rel-jump", type=float, default=0.01,
                     help="--speckle-size, --gap-size: neighbours are linked up to this relative depth difference")
+    ap.add_argument("--photo-ncc", type=float, default=None,
+                    help="photometric check before the fusion: a source agrees at a windowed ZNCC of at least this")
+    ap.add_argument("--photo-radius", type=int, default=2, help="--photo-ncc: the window is 2 R + 1 pixels wide (1..5)")
+    ap.add_argument("--photo-min-consistent", type=int, default=2, help="--photo-ncc: agreeing sources a pixel needs")
+    ap.add_argument("--photo-min-variance", type=float, default=25.0,
+                    help="--photo-ncc: least grey-level variance of a window that is scored")
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args()
     if args.save_mesh_depth and not args.mesh:
@@ -182,6 +196,11 @@ def main():
         fuse_kwargs = dict(geo_kwargs, method="roundtrip")
     if args.normals:
         fuse_kwargs.update(with_normals=True, normal_step=args.normal_step)
+    photo = None
+    if args.photo_ncc is not None:
+        photo = {"sources": sources, "radius": args.photo_radius, "min_variance": args.photo_min_variance,
+                 "ncc_threshold": args.photo_ncc, "num_consistent": args.photo_min_consistent}
+        fuse_kwargs["photo"] = photo
     low_grid_kwargs = dict(fuse_kwargs)
     upsample = None
     if args.upsample:
@@ -215,6 +234,11 @@ def main():
            "kept_share_per_view": [k / float(filtered[0].numel()) for k in kept.cpu().tolist()]}
     if clean_depth is not None:
         out["depth_cleaning"] = dict(clean_depth, report=acc.last_depth_report)
+    if photo is not None:
+        out["photometric"] = dict({k: v for k, v in photo.items() if k != "sources"}, num_src=args.num_src,
+                                  report=acc.last_photo_report)
+        print("photometric: %(valid)d valid pixels, %(scorable)d scorable, %(kept)d kept, %(removed)d removed"
+              % acc.last_photo_report["total"], file=sys.stderr)
     low_grid_points = None
     if upsample is not None:
         low_grid_points = acc.fuse(**low_grid_kwargs)[0]
@@ -275,6 +299,12 @@ def main():
             if clean:
                 uncleaned = cloud_filter.clean_cloud(uncleaned[0], uncleaned[1], None, **clean)
             out["score_without_depth_cleaning"] = evaluation.evaluate_point_cloud(uncleaned[0], gt, **kw)
+        if photo is not None:                                # the same fusion and cloud cleaning without the photometric check
+            unchecked = acc.fuse(**{k: v for k, v in fuse_kwargs.items() if k != "photo"})
+            if clean:
+                unchecked = cloud_filter.clean_cloud(unchecked[0], unchecked[1], None, **clean)
+            out["photometric"]["points_without"] = int(unchecked[0].shape[0])
+            out["score_without_photometric"] = evaluation.evaluate_point_cloud(unchecked[0], gt, **kw)
         if low_grid_points is not None:
             out["upsample"]["score_low_grid"] = evaluation.evaluate_point_cloud(low_grid_points, gt, **kw)
             out["upsample"]["score_high_grid"] = out["score_before_cleaning"] if clean else out["score"]
