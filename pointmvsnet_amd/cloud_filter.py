@@ -72,7 +72,7 @@ def _count_arg(value, who, what):
 
 def _search_grid(points, R, cells=CELLS_PER_RADIUS):
     """The sorted grid with ``cells`` cells to the radius: the cube of that many rings covers ``R`` with the 0.05-cell margin
-    of csrc/cloud_eval.hip (a cloud of more than 2^17 such cells per axis gets wider ones: fewer rings, same result)."""
+    of csrc/pf_cloud_grid.h (a cloud of more than 2^17 such cells per axis gets wider ones: fewer rings, same result)."""
     return _Grid(points, float(R) / (cells - 0.05) * (1.0 + 1e-4), hashed=False)
 
 

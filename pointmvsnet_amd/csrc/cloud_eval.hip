@@ -6,13 +6,10 @@
 // cloud_pack_kernel gathers the points into that order as 16-byte records (x, y, z, tag).  There is no cell table: the cells
 // (cx, cy, z0 .. z1) of one grid column are CONSECUTIVE keys, so the points of a z-run are one contiguous range of the
 // sorted array, found by one binary search on the per-point keys and walked until the key leaves the run.  A 3 x 3 x 3
-// neighbourhood costs 9 searches.
-//
-// Cell arithmetic is float32 and can be off by rounding: with at most 2^17 cells per axis (the host widens the cells of
-// a larger cloud) a computed cell coordinate is within 2^-23 * 2^17 < 0.016 cells of the true quotient.  Every bound below
-// keeps a margin for it: the thinning grid's edge is 1.05 * min_dist (two points nearer than min_dist differ by < 0.99 in
-// the quotient, so by at most 1 in the cell), and a search that has visited the cube of radius r around the query's cell
-// only trusts a best distance <= (r - 0.05) cells.
+// neighbourhood costs 9 searches.  That walk (walk_cube, walk_cube_wave), the margin every search keeps for the float32
+// rounding of the cell coordinates (< 0.016 cells) and the two passes of the nearest search are stated in pf_cloud_grid.h.
+// The thinning keeps the same margin through its grid's edge of 1.05 * min_dist: two points nearer than min_dist differ
+// by < 0.99 in the quotient, so by at most 1 in the cell.
 //
 //   cloud_keys       one thread per point: the cell key.
 //   cloud_pack       one thread per sorted slot: the point's record; tag = prio(original index) (thinning) or the index.
@@ -20,11 +17,9 @@
 //                    neighbours of lower priority in the PREVIOUS round's states; it is removed if one is kept, kept if all
 //                    are removed.  States are double-buffered, so the number of rounds is reproducible; the fixed point
 //                    is the sequential greedy set whatever the order (a decision, once made, is the greedy walk's).
-//   cloud_nn_cells   one thread per query on the fine grid: cubes of radius 1, 3, .. `rings` cells; finished when the
-//                    best distance is inside the visited cube (or the cube covers max_dist).  The others are left to
-//   cloud_nn_wave    one WAVE per unfinished query on a coarse grid (edge >= 1.05 * max_dist, 27 cells hold everything
-//                    within max_dist): the 64 lanes stride over each z-run; lane minima are merged by (distance, index).
-//                    This is what keeps the outliers (which would walk 41^3 fine cells each) from setting the run time.
+//   cloud_nn_cells / cloud_nn_wave   pf_cloud_grid.h's two passes over the point records (CloudNearest): a thread per query on
+//                    the fine grid, a WAVE per unfinished query on the coarse grid (edge >= 1.05 * max_dist), minima by
+//                    (distance, index).  The wave pass keeps the outliers (41^3 fine cells each) from setting the run time.
 //   cloud_obs_mask / cloud_above_plane   the two DTU filters.
 // No float atomics, no LDS, no scratch; every load is guarded by the array length.  Two runs give identical bytes.
 #include "pf_cloud_grid.h"
@@ -70,68 +65,65 @@ __global__ __launch_bounds__(256) void cloud_thin_round_kernel(const CloudPoint*
     return;
   }
   const CloudPoint p = packed[i];
-  const int64_t k = keys[i];
-  const int cx = (int)(k >> (2 * kCoordBits)), cy = (int)((k >> kCoordBits) & kCoordMask), cz = (int)(k & kCoordMask);
-  const int z0 = max(cz - 1, 0), z1 = min(cz + 1, nz - 1);
+  int cx, cy, cz;
+  cell_of_key(keys[i], cx, cy, cz);
   bool kept_near = false, undecided_near = false;
-  for (int x = max(cx - 1, 0); x <= min(cx + 1, nx - 1) && !kept_near; ++x) {
-    for (int y = max(cy - 1, 0); y <= min(cy + 1, ny - 1) && !kept_near; ++y) {
-      const int64_t khi = cell_key(x, y, z1);
-      for (int j = lower_bound(keys, n, cell_key(x, y, z0)); j < n && keys[j] <= khi; ++j) {
-        const CloudPoint q = packed[j];
-        if (q.tag < p.tag && dist2(p.x, p.y, p.z, q.x, q.y, q.z) < t) {      // tags are a bijection of the index: j != i
-          const unsigned char sj = state_in[j];
-          kept_near |= sj == kKept;
-          undecided_near |= sj == kUndecided;
-        }
-      }
+  walk_cube(keys, n, nx, ny, nz, cx, cy, cz, 1, [&](int j) {
+    const CloudPoint q = packed[j];
+    if (q.tag < p.tag && dist2(p.x, p.y, p.z, q.x, q.y, q.z) < t) {        // tags are a bijection of the index: j != i
+      const unsigned char sj = state_in[j];
+      kept_near |= sj == kKept;
+      undecided_near |= sj == kUndecided;
     }
-  }
+    return !kept_near;                                                     // one kept neighbour decides
+  });
   const unsigned char out = kept_near ? kRemoved : (undecided_near ? kUndecided : kKept);
   state_out[i] = out;
   if (out == kUndecided) *pending = 1;                                     // every writer stores the same value
 }
+
+// nearest_distances' policy for pf_cloud_grid.h's two passes: float32 d2, ties to the lower tag (the original index)
+struct CloudNearest {
+  const CloudPoint* __restrict__ packed;
+  float* __restrict__ dist;
+  int* __restrict__ index;
+  float qx, qy, qz, best;
+  unsigned best_tag;
+
+  __device__ __forceinline__ void start(float x, float y, float z) {
+    qx = x, qy = y, qz = z;
+    best = INFINITY;
+    best_tag = 0xffffffffu;
+  }
+  __device__ __forceinline__ void take(float d2, unsigned tag) {
+    if (d2 < best || (d2 == best && tag < best_tag)) {
+      best = d2;
+      best_tag = tag;
+    }
+  }
+  __device__ __forceinline__ void offer(int j) {
+    const CloudPoint p = packed[j];
+    take(dist2(qx, qy, qz, p.x, p.y, p.z), p.tag);
+  }
+  __device__ __forceinline__ bool within(float reach) const { return best <= reach * reach; }
+  __device__ __forceinline__ void merge(int off) {
+    const float ob = __shfl_xor(best, off);
+    const unsigned ot = __shfl_xor(best_tag, off);
+    take(ob, ot);
+  }
+  __device__ __forceinline__ void write(int64_t i, float max_dist) const {
+    const float d = fminf(sqrtf(best), max_dist);
+    dist[i] = d;
+    index[i] = d < max_dist ? (int)best_tag : -1;
+  }
+};
 
 __global__ __launch_bounds__(256) void cloud_nn_cells_kernel(const float* __restrict__ query, int64_t nq,
                                                              const CloudPoint* __restrict__ packed,
                                                              const int64_t* __restrict__ keys, int nt, CloudGrid g, int rings,
                                                              float max_dist, float* __restrict__ dist, int* __restrict__ index,
                                                              unsigned char* __restrict__ done) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= nq) return;
-  const float qx = query[i * 3 + 0], qy = query[i * 3 + 1], qz = query[i * 3 + 2];
-  // a query more than `rings` cells outside the grid meets no cell at all: it stays unfinished
-  const int cx = cell_coord(qx, g.ox, g.edge, -(rings + 1), g.nx + rings);
-  const int cy = cell_coord(qy, g.oy, g.edge, -(rings + 1), g.ny + rings);
-  const int cz = cell_coord(qz, g.oz, g.edge, -(rings + 1), g.nz + rings);
-  float best = INFINITY;
-  unsigned best_tag = 0xffffffffu;
-  bool finished = false;
-  for (int r = 1; r <= rings && !finished; r += 2) {
-    const int z0 = max(cz - r, 0), z1 = min(cz + r, g.nz - 1);
-    if (z0 <= z1) {
-      for (int x = max(cx - r, 0); x <= min(cx + r, g.nx - 1); ++x) {
-        for (int y = max(cy - r, 0); y <= min(cy + r, g.ny - 1); ++y) {
-          const int64_t khi = cell_key(x, y, z1);
-          for (int j = lower_bound(keys, nt, cell_key(x, y, z0)); j < nt && keys[j] <= khi; ++j) {
-            const CloudPoint p = packed[j];
-            const float d2 = dist2(qx, qy, qz, p.x, p.y, p.z);
-            if (d2 < best || (d2 == best && p.tag < best_tag)) {
-              best = d2;
-              best_tag = p.tag;
-            }
-          }
-        }
-      }
-    }
-    const float reach = ((float)r - 0.05f) * g.edge;       // everything nearer than this has been visited
-    finished = best <= reach * reach || reach >= max_dist;
-  }
-  done[i] = finished ? 1 : 0;
-  if (!finished) return;
-  const float d = fminf(sqrtf(best), max_dist);
-  dist[i] = d;
-  index[i] = d < max_dist ? (int)best_tag : -1;
+  nearest_cells_pass(CloudNearest{packed, dist, index}, query, nq, keys, nt, g, rings, max_dist, done);
 }
 
 __global__ __launch_bounds__(256) void cloud_nn_wave_kernel(const float* __restrict__ query, const int64_t* __restrict__ todo,
@@ -139,47 +131,7 @@ __global__ __launch_bounds__(256) void cloud_nn_wave_kernel(const float* __restr
                                                             const int64_t* __restrict__ keys, int nt, CloudGrid g,
                                                             float max_dist, float* __restrict__ dist,
                                                             int* __restrict__ index) {
-  const int64_t w = ((int64_t)blockIdx.x * 256 + threadIdx.x) / PF_WAVE;       // uniform over the wave
-  const int lane = threadIdx.x & (PF_WAVE - 1);
-  if (w >= ntodo) return;
-  const int64_t i = todo[w];
-  if (i < 0 || i >= nq) return;
-  const float qx = query[i * 3 + 0], qy = query[i * 3 + 1], qz = query[i * 3 + 2];
-  const int cx = cell_coord(qx, g.ox, g.edge, -2, g.nx + 1);
-  const int cy = cell_coord(qy, g.oy, g.edge, -2, g.ny + 1);
-  const int cz = cell_coord(qz, g.oz, g.edge, -2, g.nz + 1);
-  float best = INFINITY;
-  unsigned best_tag = 0xffffffffu;
-  const int z0 = max(cz - 1, 0), z1 = min(cz + 1, g.nz - 1);
-  if (z0 <= z1) {
-    for (int x = max(cx - 1, 0); x <= min(cx + 1, g.nx - 1); ++x) {
-      for (int y = max(cy - 1, 0); y <= min(cy + 1, g.ny - 1); ++y) {
-        const int j0 = lower_bound(keys, nt, cell_key(x, y, z0));
-        const int j1 = lower_bound(keys, nt, cell_key(x, y, z1) + 1);
-        for (int j = j0 + lane; j < j1; j += PF_WAVE) {
-          const CloudPoint p = packed[j];
-          const float d2 = dist2(qx, qy, qz, p.x, p.y, p.z);
-          if (d2 < best || (d2 == best && p.tag < best_tag)) {
-            best = d2;
-            best_tag = p.tag;
-          }
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int off = PF_WAVE / 2; off >= 1; off >>= 1) {
-    const float ob = __shfl_xor(best, off);
-    const unsigned ot = __shfl_xor(best_tag, off);
-    if (ob < best || (ob == best && ot < best_tag)) {
-      best = ob;
-      best_tag = ot;
-    }
-  }
-  if (lane != 0) return;
-  const float d = fminf(sqrtf(best), max_dist);
-  dist[i] = d;
-  index[i] = d < max_dist ? (int)best_tag : -1;
+  nearest_wave_pass(CloudNearest{packed, dist, index}, query, todo, ntodo, nq, keys, nt, g, max_dist);
 }
 
 __global__ __launch_bounds__(256) void cloud_obs_mask_kernel(const float* __restrict__ points, int64_t n,

@@ -4,14 +4,14 @@
 //
 //   cloud_knn_stats<K>  one thread per point IN SORTED ORDER (neighbouring threads walk the same z-runs); the thread's own
 //                       record and key come from the sorted arrays and its cell from the key.  It visits the cube of radius
-//                       r cells around its cell, r = 1, 2, ..: the K smallest d2 < R2 among the other points
+//                       r cells around its cell (walk_cube), r = 1, 2, ..: the K smallest d2 < R2 among the other points
 //                       (other by TAG, so an exact duplicate counts at distance 0) sit in K registers, ascending: a candidate
 //                       below the current worst is passed down the array by min / max, every index static.  A ring is final
-//                       when the k-th best is <= (r - 0.05) cells (the rule of cloud_nn_cells: nothing outside the cube can
+//                       when the k-th best is <= (r - 0.05) cells (pf_cloud_grid.h's margin: nothing outside the cube can
 //                       be nearer) or when that reach covers R; every ring starts over, so nothing is inserted twice.  The
 //                       result -- a multiset and a fixed summation order -- does not depend on the order the candidates
 //                       arrive in, hence not on the grid.  Results scatter back through the tag.
-//   cloud_radius_count  the same walk, counting only, and final once `limit` neighbours are found.
+//   cloud_radius_count  the same walk, counting only; its visitor ends the walk once `limit` neighbours are found.
 //   cloud_voxel_keys    one thread per point: the voxel key from floor((p - o) * inv), inv made by the host.
 //   cloud_voxel_reduce  one thread per voxel over its run of the (stably) sorted order: float64 sums in ascending input
 //                       index, integer colour sums; writes the voxel's row and its members' inverse-map entries.
@@ -28,8 +28,8 @@ __global__ __launch_bounds__(256) void cloud_knn_stats_kernel(const CloudPoint* 
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const CloudPoint p = packed[i];
-  const int64_t key = keys[i];
-  const int cx = (int)(key >> (2 * kCoordBits)), cy = (int)((key >> kCoordBits) & kCoordMask), cz = (int)(key & kCoordMask);
+  int cx, cy, cz;
+  cell_of_key(keys[i], cx, cy, cz);
   const int whole = max(nx, max(ny, nz));                  // a cube of this radius is the whole grid
   float a[K];
   int found = 0;
@@ -38,26 +38,21 @@ __global__ __launch_bounds__(256) void cloud_knn_stats_kernel(const CloudPoint* 
 #pragma unroll
     for (int s = 0; s < K; ++s) a[s] = INFINITY;
     found = 0;
-    const int z0 = max(cz - r, 0), z1 = min(cz + r, nz - 1);
-    for (int x = max(cx - r, 0); x <= min(cx + r, nx - 1); ++x) {
-      for (int y = max(cy - r, 0); y <= min(cy + r, ny - 1); ++y) {
-        const int64_t khi = cell_key(x, y, z1);
-        for (int j = lower_bound(keys, n, cell_key(x, y, z0)); j < n && keys[j] <= khi; ++j) {
-          const CloudPoint q = packed[j];
-          float d = dist2(p.x, p.y, p.z, q.x, q.y, q.z);
-          if (q.tag == p.tag || !(d < R2)) continue;
-          ++found;
-          if (d < a[K - 1]) {
+    walk_cube(keys, n, nx, ny, nz, cx, cy, cz, r, [&](int j) {
+      const CloudPoint q = packed[j];
+      float d = dist2(p.x, p.y, p.z, q.x, q.y, q.z);
+      if (q.tag == p.tag || !(d < R2)) return true;
+      ++found;
+      if (d < a[K - 1]) {
 #pragma unroll
-            for (int s = 0; s < K; ++s) {
-              const float lo = fminf(a[s], d);
-              d = fmaxf(a[s], d);
-              a[s] = lo;
-            }
-          }
+        for (int s = 0; s < K; ++s) {
+          const float lo = fminf(a[s], d);
+          d = fmaxf(a[s], d);
+          a[s] = lo;
         }
       }
-    }
+      return true;
+    });
     const float reach = ((float)r - 0.05f) * edge;         // everything nearer than this has been visited
     float kth = INFINITY;                                  // the k-th best, INFINITY while fewer are found
 #pragma unroll
@@ -84,23 +79,18 @@ __global__ __launch_bounds__(256) void cloud_radius_count_kernel(const CloudPoin
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const CloudPoint p = packed[i];
-  const int64_t key = keys[i];
-  const int cx = (int)(key >> (2 * kCoordBits)), cy = (int)((key >> kCoordBits) & kCoordMask), cz = (int)(key & kCoordMask);
+  int cx, cy, cz;
+  cell_of_key(keys[i], cx, cy, cz);
   const int whole = max(nx, max(ny, nz));
   int found = 0;
   bool finished = false;
   for (int r = 1; !finished; ++r) {
     found = 0;
-    const int z0 = max(cz - r, 0), z1 = min(cz + r, nz - 1);
-    for (int x = max(cx - r, 0); x <= min(cx + r, nx - 1) && found < limit; ++x) {
-      for (int y = max(cy - r, 0); y <= min(cy + r, ny - 1) && found < limit; ++y) {
-        const int64_t khi = cell_key(x, y, z1);
-        for (int j = lower_bound(keys, n, cell_key(x, y, z0)); j < n && keys[j] <= khi && found < limit; ++j) {
-          const CloudPoint q = packed[j];
-          if (q.tag != p.tag && dist2(p.x, p.y, p.z, q.x, q.y, q.z) < R2) ++found;
-        }
-      }
-    }
+    walk_cube(keys, n, nx, ny, nz, cx, cy, cz, r, [&](int j) {
+      const CloudPoint q = packed[j];
+      if (q.tag != p.tag && dist2(p.x, p.y, p.z, q.x, q.y, q.z) < R2) ++found;
+      return found < limit;                                // the walk ends at the limit-th neighbour: found <= limit
+    });
     finished = found >= limit || ((float)r - 0.05f) * edge >= R || r >= whole;
   }
   if (p.tag < (unsigned)n) count[p.tag] = found;

@@ -3,9 +3,10 @@
 //
 // The search structure is cloud_eval.hip's sorted sparse grid (pf_cloud_grid.h) with a (cell, face) PAIR for a point: a face
 // is listed in every cell of the box lo .. hi, lo = cell(min over its vertices - margin), hi = cell(max + margin) per axis,
-// margin = kBoxMargin * edge in float32.  Why a search may trust that list: let c be the point of a face nearest to the
-// query q and T(x) = (x - origin) / edge the true quotient per axis.  A computed cell coordinate is floor(T + e) with
-// |e| < 0.016 (at most 2^17 cells per axis, pf_cloud_grid.h), so lo <= floor(T(min) - 0.02 + 0.016) <= floor(T(c)) <= hi:
+// margin = kBoxMargin * edge in float32.  The search is pf_cloud_grid.h's, whose margin comment argues for points; why it
+// may trust a list of boxes: let c be the point of a face nearest to the query q and T(x) = (x - origin) / edge the true
+// quotient per axis.  A computed cell coordinate is floor(T + e) with |e| < 0.016 (at most 2^17 cells per axis,
+// pf_cloud_grid.h), so lo <= floor(T(min) - 0.02 + 0.016) <= floor(T(c)) <= hi:
 // the face is listed in the cell floor(T(c)).  If |c - q| <= (r - 0.05) edge, then T(c) < T~(q) + 0.016 + r - 0.05 < T~(q) + r
 // with T~ the computed quotient of q, so floor(T(c)) lies within r of q's computed cell, on both sides: a search that has
 // walked the cube of radius r cells around q's cell has met every face nearer than (r - 0.05) edge.  (The float64 d2 is
@@ -18,10 +19,9 @@
 //                     cell by its rank in the face's box: the cell key and the face index.  The host sorts the keys.
 //   mesh_dist_pack    one thread per sorted slot: the 48-byte record (a, face index; b; c), so that the inner loops below
 //                     have no dependent index load.
-//   mesh_dist_cells   one thread per query on the fine grid: cubes of radius 1, 3, .. `rings` cells; finished when the best
-//                     distance lies inside the visited cube (or the cube covers max_dist).  The others are left to
-//   mesh_dist_wave    one WAVE per unfinished query on a coarse grid (edge >= 1.05 * max_dist: 27 cells list every face
-//                     within max_dist); the 64 lanes stride over each z-run and merge by (d2, face index) through shuffles.
+//   mesh_dist_cells / mesh_dist_wave   pf_cloud_grid.h's two passes over the face records (MeshNearest): a thread per query on
+//                     the fine grid, a WAVE per unfinished query on the coarse grid (edge >= 1.05 * max_dist: 27 cells list
+//                     every face within max_dist), minima by (d2, face index).
 // No atomics, no LDS, no scratch (no per-thread stack: that is why this is a grid and not a tree); every load is guarded by
 // its array's length.  Two runs give identical bytes.
 #include "pf_cloud_grid.h"
@@ -181,57 +181,51 @@ __device__ __forceinline__ double face_d2(const Vec3& p, const FaceRecord& r) {
   return d2;
 }
 
-// (d2, face) is better than (best, best_face): false for a NaN d2
-__device__ __forceinline__ bool better(double d2, int face, double best, int best_face) {
-  return d2 < best || (d2 == best && (unsigned)face < (unsigned)best_face);
-}
+// point_mesh_distances' policy for pf_cloud_grid.h's two passes: float64 d2, the lexicographic minimum of (d2, face index)
+struct MeshNearest {
+  const FaceRecord* __restrict__ records;
+  float* __restrict__ dist;
+  int* __restrict__ face;
+  Vec3 p;
+  double best;
+  int best_face;
 
-__device__ __forceinline__ void write_result(double best, int best_face, float max_dist, int64_t i, float* __restrict__ dist,
-                                             int* __restrict__ face) {
-  const float d = (float)sqrt(best);
-  const bool capped = !(d < max_dist) || best_face < 0;
-  dist[i] = capped ? max_dist : d;
-  face[i] = capped ? -1 : best_face;
-}
+  __device__ __forceinline__ void start(float x, float y, float z) {
+    p = {(double)x, (double)y, (double)z};
+    best = INFINITY;
+    best_face = -1;
+  }
+  // (d2, f) replaces the best where it is better: never for a NaN d2
+  __device__ __forceinline__ void take(double d2, int f) {
+    if (d2 < best || (d2 == best && (unsigned)f < (unsigned)best_face)) {
+      best = d2;
+      best_face = f;
+    }
+  }
+  __device__ __forceinline__ void offer(int j) {
+    const FaceRecord rec = records[j];
+    take(face_d2(p, rec), rec.face);
+  }
+  __device__ __forceinline__ bool within(float reach) const { return best <= (double)reach * (double)reach; }
+  __device__ __forceinline__ void merge(int off) {
+    const double ob = __shfl_xor(best, off);
+    const int of = __shfl_xor(best_face, off);
+    take(ob, of);
+  }
+  __device__ __forceinline__ void write(int64_t i, float max_dist) const {
+    const float d = (float)sqrt(best);
+    const bool capped = !(d < max_dist) || best_face < 0;
+    dist[i] = capped ? max_dist : d;
+    face[i] = capped ? -1 : best_face;
+  }
+};
 
 __global__ __launch_bounds__(256) void mesh_dist_cells_kernel(const float* __restrict__ query, int64_t nq,
                                                               const FaceRecord* __restrict__ records,
                                                               const int64_t* __restrict__ keys, int np, CloudGrid g, int rings,
                                                               float max_dist, float* __restrict__ dist, int* __restrict__ face,
                                                               unsigned char* __restrict__ done) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= nq) return;
-  const float qx = query[i * 3 + 0], qy = query[i * 3 + 1], qz = query[i * 3 + 2];
-  const Vec3 p = {(double)qx, (double)qy, (double)qz};
-  // a query more than `rings` cells outside the grid meets no cell at all: it stays unfinished
-  const int cx = cell_coord(qx, g.ox, g.edge, -(rings + 1), g.nx + rings);
-  const int cy = cell_coord(qy, g.oy, g.edge, -(rings + 1), g.ny + rings);
-  const int cz = cell_coord(qz, g.oz, g.edge, -(rings + 1), g.nz + rings);
-  double best = INFINITY;
-  int best_face = -1;
-  bool finished = false;
-  for (int r = 1; r <= rings && !finished; r += 2) {
-    const int z0 = max(cz - r, 0), z1 = min(cz + r, g.nz - 1);
-    if (z0 <= z1) {
-      for (int x = max(cx - r, 0); x <= min(cx + r, g.nx - 1); ++x) {
-        for (int y = max(cy - r, 0); y <= min(cy + r, g.ny - 1); ++y) {
-          const int64_t khi = cell_key(x, y, z1);
-          for (int j = lower_bound(keys, np, cell_key(x, y, z0)); j < np && keys[j] <= khi; ++j) {
-            const FaceRecord rec = records[j];
-            const double d2 = face_d2(p, rec);
-            if (better(d2, rec.face, best, best_face)) {
-              best = d2;
-              best_face = rec.face;
-            }
-          }
-        }
-      }
-    }
-    const float reach = ((float)r - 0.05f) * g.edge;       // every face nearer than this has been met
-    finished = best <= (double)reach * (double)reach || reach >= max_dist;
-  }
-  done[i] = finished ? 1 : 0;
-  if (finished) write_result(best, best_face, max_dist, i, dist, face);
+  nearest_cells_pass(MeshNearest{records, dist, face}, query, nq, keys, np, g, rings, max_dist, done);
 }
 
 __global__ __launch_bounds__(256) void mesh_dist_wave_kernel(const float* __restrict__ query, const int64_t* __restrict__ todo,
@@ -239,45 +233,7 @@ __global__ __launch_bounds__(256) void mesh_dist_wave_kernel(const float* __rest
                                                              const int64_t* __restrict__ keys, int np, CloudGrid g,
                                                              float max_dist, float* __restrict__ dist,
                                                              int* __restrict__ face) {
-  const int64_t w = ((int64_t)blockIdx.x * 256 + threadIdx.x) / PF_WAVE;       // uniform over the wave
-  const int lane = threadIdx.x & (PF_WAVE - 1);
-  if (w >= ntodo) return;
-  const int64_t i = todo[w];
-  if (i < 0 || i >= nq) return;
-  const float qx = query[i * 3 + 0], qy = query[i * 3 + 1], qz = query[i * 3 + 2];
-  const Vec3 p = {(double)qx, (double)qy, (double)qz};
-  const int cx = cell_coord(qx, g.ox, g.edge, -2, g.nx + 1);
-  const int cy = cell_coord(qy, g.oy, g.edge, -2, g.ny + 1);
-  const int cz = cell_coord(qz, g.oz, g.edge, -2, g.nz + 1);
-  double best = INFINITY;
-  int best_face = -1;
-  const int z0 = max(cz - 1, 0), z1 = min(cz + 1, g.nz - 1);
-  if (z0 <= z1) {
-    for (int x = max(cx - 1, 0); x <= min(cx + 1, g.nx - 1); ++x) {
-      for (int y = max(cy - 1, 0); y <= min(cy + 1, g.ny - 1); ++y) {
-        const int j0 = lower_bound(keys, np, cell_key(x, y, z0));
-        const int j1 = lower_bound(keys, np, cell_key(x, y, z1) + 1);
-        for (int j = j0 + lane; j < j1; j += PF_WAVE) {
-          const FaceRecord rec = records[j];
-          const double d2 = face_d2(p, rec);
-          if (better(d2, rec.face, best, best_face)) {
-            best = d2;
-            best_face = rec.face;
-          }
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int off = PF_WAVE / 2; off >= 1; off >>= 1) {
-    const double ob = __shfl_xor(best, off);
-    const int of = __shfl_xor(best_face, off);
-    if (better(ob, of, best, best_face)) {
-      best = ob;
-      best_face = of;
-    }
-  }
-  if (lane == 0) write_result(best, best_face, max_dist, i, dist, face);
+  nearest_wave_pass(MeshNearest{records, dist, face}, query, todo, ntodo, nq, keys, np, g, max_dist);
 }
 
 inline bool dist_sizes_ok(int64_t Nv, int64_t Nf) {

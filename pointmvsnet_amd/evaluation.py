@@ -36,9 +36,9 @@ from . import _lib
 
 MAX_CELLS = 1 << 17          # PF_CLOUD_MAX_CELLS of include/pointflow_hip.h
 MAX_POINTS = 2000000000      # PF_CLOUD_MAX_POINTS
-MARGIN = 1.05                # cell edge / search radius: covers the float32 rounding of the cell coordinates (cloud_eval.hip)
+MARGIN = 1.05                # cell edge / search radius: covers the float32 rounding of the cell coordinates (pf_cloud_grid.h)
 FINE_CELLS_PER_MAX_DIST = 40  # the fine search grid: max_dist / 40 = 0.5 at DTU's 20
-FINE_RINGS = 3
+FINE_RINGS = 3               # the first pass walks the cubes of radius 1 and 3 cells
 
 _last_rounds = 0
 _last_unfinished = 0
@@ -71,6 +71,14 @@ def _check_points(points, what, gpu=True):
     return points
 
 
+def _grid_frame(lo, hi, edge):
+    """``(edge, origin, cells)`` of the search grid over the float64 box ``lo .. hi`` with the cell edge wanted: the edge is
+    widened until the box fits into ``MAX_CELLS - 4`` cells and rounded to float32, the origin is the box's float32 corner and
+    every axis gets ``floor(extent / edge) + 2`` cells (the upper corner's own cell and one of slack)."""
+    edge = float(np.float32(max(float(edge), float((hi - lo).max()) / (MAX_CELLS - 4))))
+    return edge, [float(v) for v in lo.astype(np.float32)], [int(np.floor(e / edge)) + 2 for e in (hi - lo)]
+
+
 class _Grid(object):
     """A cloud sorted into a sparse grid of cell edge >= ``edge``: ``keys`` (sorted), ``packed`` (N, 4) records, ``order``."""
 
@@ -79,11 +87,7 @@ class _Grid(object):
         dev = points.device
         lo = points.amin(dim=0).cpu().numpy().astype(np.float64)       # plumbing: the bounding box
         hi = points.amax(dim=0).cpu().numpy().astype(np.float64)
-        extent = float((hi - lo).max())
-        edge = np.float32(max(float(edge), extent / (MAX_CELLS - 4)))
-        self.edge = float(edge)
-        self.origin = [float(v) for v in lo.astype(np.float32)]
-        self.cells = [int(np.floor(e / float(edge))) + 2 for e in (hi - lo)]
+        self.edge, self.origin, self.cells = _grid_frame(lo, hi, edge)
         self.n = n
         keys = torch.empty((n,), dtype=torch.int64, device=dev)
         _lib.call("pf_cloud_cell_keys_f32", _lib.ptr(points), n, *(self.origin + [self.edge] + self.cells +
@@ -134,6 +138,35 @@ def thin_points(points, min_dist=0.2, return_index=False):
     return (kept, idx) if return_index else kept
 
 
+def _two_pass_search(query, cap, make_grid, first_pass, second_pass, dist, index):
+    """The search of ``nearest_distances`` and ``mesh_distance.point_mesh_distances`` into ``dist`` / ``index``:
+    ``make_grid(edge)`` sorts the target into a grid; ``first_pass`` (a thread per query on the fine grid, edge ``cap / 40``)
+    marks in ``done`` what it finishes; the rest goes to ``second_pass`` (a wave per query) on the coarse grid of edge
+    ``1.05 cap``, built only when needed.  Returns ``(fine, coarse or None, number of second-pass queries)``."""
+    fine = make_grid(cap / FINE_CELLS_PER_MAX_DIST)
+    coarse, unfinished = None, 0
+    if fine.keys.numel():                                              # no record (no face has a surface): nothing to find
+        done = torch.empty((int(query.shape[0]),), dtype=torch.uint8, device=query.device)
+        first_pass(query, fine, cap, dist, index, done)
+        todo = torch.nonzero(done == 0).view(-1)                       # plumbing: the list of unfinished queries
+        unfinished = int(todo.numel())
+        if unfinished:
+            coarse = make_grid(cap * MARGIN)
+            second_pass(query, todo, coarse, cap, dist, index)
+    return fine, coarse, unfinished
+
+
+def _first_pass(query, grid, cap, dist, index, done):
+    _lib.call("pf_cloud_nn_cells_f32", _lib.ptr(query), int(query.shape[0]), _lib.ptr(grid.packed), _lib.ptr(grid.keys), grid.n,
+              *(grid.args() + [FINE_RINGS, cap, _lib.ptr(dist), _lib.ptr(index), _lib.ptr(done), _lib.stream()]))
+
+
+def _second_pass(query, todo, grid, cap, dist, index):
+    _lib.call("pf_cloud_nn_wave_f32", _lib.ptr(query), _lib.ptr(todo), int(todo.numel()), int(query.shape[0]),
+              _lib.ptr(grid.packed), _lib.ptr(grid.keys), grid.n,
+              *(grid.args() + [cap, _lib.ptr(dist), _lib.ptr(index), _lib.stream()]))
+
+
 def nearest_distances(query, target, max_dist=20.0, return_index=False):
     """Per point of ``query`` (Nq, 3) its distance to the nearest point of ``target`` (Nt, 3), capped at ``max_dist`` (module
     docstring, 2.): float32 (Nq,); with ``return_index`` also the int64 index of that target point (-1 at the cap)."""
@@ -152,17 +185,8 @@ def nearest_distances(query, target, max_dist=20.0, return_index=False):
         dist = torch.full((nq,), cap, dtype=torch.float32, device=dev)
         index = torch.full((nq,), -1, dtype=torch.int32, device=dev)
         if nq and nt:
-            fine = _Grid(target, cap / FINE_CELLS_PER_MAX_DIST, hashed=False)
-            done = torch.empty((nq,), dtype=torch.uint8, device=dev)
-            _lib.call("pf_cloud_nn_cells_f32", _lib.ptr(query), nq, _lib.ptr(fine.packed), _lib.ptr(fine.keys), nt,
-                      *(fine.args() + [FINE_RINGS, cap, _lib.ptr(dist), _lib.ptr(index), _lib.ptr(done), _lib.stream()]))
-            todo = torch.nonzero(done == 0).view(-1)                   # plumbing: the list of unfinished queries
-            _last_unfinished = int(todo.numel())
-            if _last_unfinished:
-                coarse = _Grid(target, cap * MARGIN, hashed=False)
-                _lib.call("pf_cloud_nn_wave_f32", _lib.ptr(query), _lib.ptr(todo), _last_unfinished, nq,
-                          _lib.ptr(coarse.packed), _lib.ptr(coarse.keys), nt,
-                          *(coarse.args() + [cap, _lib.ptr(dist), _lib.ptr(index), _lib.stream()]))
+            _last_unfinished = _two_pass_search(query, cap, lambda edge: _Grid(target, edge, hashed=False), _first_pass,
+                                                _second_pass, dist, index)[2]
     return (dist, index.long()) if return_index else dist
 
 
@@ -202,6 +226,40 @@ def _mean_median(d):
     return float(d.double().sum() / d.numel()), float(torch.median(d))
 
 
+def _scores(d_acc, acc_points, d_comp, comp_points, cap, counts, tensors, obs_mask, bb_min, res, plane):
+    """The scoring tail of every ``evaluate_*`` route, here and in mesh_distance.py.  ``d_acc`` (measured from ``acc_points``)
+    is used below the cap and inside ``obs_mask``, ``d_comp`` (from ``comp_points``) below the cap and above ``plane``.  The
+    dict holds the five scores, ``counts`` and the two used counts; with ``tensors`` (for ``return_distances``, else None)
+    also those, the two distance tensors and the two masks."""
+    acc_used = d_acc < cap
+    if obs_mask is not None:
+        acc_used &= in_obs_mask(acc_points, obs_mask, bb_min, res)
+    comp_used = d_comp < cap
+    if plane is not None:
+        comp_used &= above_plane(comp_points, plane)
+    acc_mean, acc_median = _mean_median(d_acc[acc_used])
+    comp_mean, comp_median = _mean_median(d_comp[comp_used])
+    out = {"accuracy_mean": acc_mean, "accuracy_median": acc_median, "completeness_mean": comp_mean,
+           "completeness_median": comp_median, "overall": (acc_mean + comp_mean) / 2.0}
+    out.update(counts)
+    out.update(n_data_used=int(acc_used.sum()), n_gt_used=int(comp_used.sum()))
+    if tensors is not None:
+        out.update(tensors, d_acc=d_acc, d_comp=d_comp, acc_used=acc_used, comp_used=comp_used)
+    return out
+
+
+def _dtu_filters(obs_mask_mat, plane_mat):
+    """DTU's ``ObsMask<scan>_10.mat`` / ``Plane<scan>.mat`` as the filter arguments of the ``evaluate_*`` functions."""
+    from .utils import io as IO
+    kw = {}
+    if obs_mask_mat is not None:
+        mask, bb_min, res = IO.load_dtu_obs_mask(obs_mask_mat)
+        kw.update(obs_mask=mask, bb_min=bb_min, res=res)
+    if plane_mat is not None:
+        kw.update(plane=IO.load_dtu_plane(plane_mat))
+    return kw
+
+
 def evaluate_point_cloud(data, gt, min_dist=0.2, max_dist=20.0, obs_mask=None, bb_min=None, res=None, plane=None, thin=True,
                          return_distances=False):
     """DTU's scores of the reconstructed cloud ``data`` against the ground-truth cloud ``gt`` as a dict of Python numbers.
@@ -221,21 +279,9 @@ def evaluate_point_cloud(data, gt, min_dist=0.2, max_dist=20.0, obs_mask=None, b
     thinned = thin_points(data, min_dist) if thin else data
     d_acc = nearest_distances(thinned, gt, max_dist)
     d_comp = nearest_distances(gt, thinned, max_dist)
-    acc_used = d_acc < cap
-    if obs_mask is not None:
-        acc_used &= in_obs_mask(thinned, obs_mask, bb_min, res)
-    comp_used = d_comp < cap
-    if plane is not None:
-        comp_used &= above_plane(gt, plane)
-    acc_mean, acc_median = _mean_median(d_acc[acc_used])
-    comp_mean, comp_median = _mean_median(d_comp[comp_used])
-    out = {"accuracy_mean": acc_mean, "accuracy_median": acc_median, "completeness_mean": comp_mean,
-           "completeness_median": comp_median, "overall": (acc_mean + comp_mean) / 2.0,
-           "n_data": int(data.shape[0]), "n_data_thinned": int(thinned.shape[0]), "n_data_used": int(acc_used.sum()),
-           "n_gt": int(gt.shape[0]), "n_gt_used": int(comp_used.sum())}
-    if return_distances:
-        out.update(data_thinned=thinned, d_acc=d_acc, d_comp=d_comp, acc_used=acc_used, comp_used=comp_used)
-    return out
+    return _scores(d_acc, thinned, d_comp, gt, cap,
+                   {"n_data": int(data.shape[0]), "n_data_thinned": int(thinned.shape[0]), "n_gt": int(gt.shape[0])},
+                   {"data_thinned": thinned} if return_distances else None, obs_mask, bb_min, res, plane)
 
 
 def evaluate_ply(data_ply, gt_ply, obs_mask_mat=None, plane_mat=None, min_dist=0.2, max_dist=20.0, thin=True, device=None,
@@ -246,10 +292,5 @@ def evaluate_ply(data_ply, gt_ply, obs_mask_mat=None, plane_mat=None, min_dist=0
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     data = torch.from_numpy(IO.load_ply_points(data_ply)).to(dev)
     gt = torch.from_numpy(IO.load_ply_points(gt_ply)).to(dev)
-    mask = bb_min = res = plane = None
-    if obs_mask_mat is not None:
-        mask, bb_min, res = IO.load_dtu_obs_mask(obs_mask_mat)
-    if plane_mat is not None:
-        plane = IO.load_dtu_plane(plane_mat)
-    return evaluate_point_cloud(data, gt, min_dist=min_dist, max_dist=max_dist, obs_mask=mask, bb_min=bb_min, res=res,
-                                plane=plane, thin=thin, return_distances=return_distances)
+    return evaluate_point_cloud(data, gt, min_dist=min_dist, max_dist=max_dist, thin=thin,
+                                return_distances=return_distances, **_dtu_filters(obs_mask_mat, plane_mat))

@@ -80,12 +80,9 @@ import numpy as np
 import torch
 
 from . import _lib, evaluation, mesh_ops
+from .evaluation import FINE_CELLS_PER_MAX_DIST, FINE_RINGS, MARGIN  # the search's grid parameters are nearest_distances'
 
 MAX_FACES = 2 ** 27 - 2 ** 13                  # PF_MESH_DIST_MAX_FACES: the budget below then stays under 2^31 pairs
-MAX_CELLS = evaluation.MAX_CELLS
-MARGIN = evaluation.MARGIN                     # coarse cell edge / max_dist
-FINE_CELLS_PER_MAX_DIST = 40
-FINE_RINGS = 3
 BUDGET_PER_FACE = 16
 BUDGET_BASE = 1 << 16
 
@@ -111,15 +108,11 @@ class _FaceGrid(object):
     def __init__(self, vertices, faces32, lo, hi, edge):
         Nv, Nf = int(vertices.shape[0]), int(faces32.shape[0])
         dev = vertices.device
-        extent = float((hi - lo).max())
-        edge = np.float32(max(float(edge), extent / (MAX_CELLS - 4)))
         budget = pair_budget(Nf)
-        self.origin = [float(v) for v in lo.astype(np.float32)]
         self.widenings = 0
         count = torch.empty((Nf,), dtype=torch.int64, device=dev)
         while True:
-            self.edge = float(edge)
-            self.cells = [int(np.floor(e / float(edge))) + 2 for e in (hi - lo)]
+            self.edge, self.origin, self.cells = evaluation._grid_frame(lo, hi, edge)
             _lib.call("pf_mesh_dist_count_f32", _lib.ptr(vertices), Nv, _lib.ptr(faces32), Nf,
                       *(self.args() + [budget + 1, _lib.ptr(count), _lib.stream()]), algo_bytes=Nf * (12 + 36 + 8))
             incl = torch.cumsum(count, dim=0)                              # plumbing
@@ -130,7 +123,7 @@ class _FaceGrid(object):
                 break
             if max(self.cells) <= 2:                                       # at most 8 pairs per face: cannot happen
                 raise RuntimeError("point_mesh_distances: %d pairs on a grid of %s cells" % (total, self.cells))
-            edge = np.float32(2.0) * edge
+            edge = 2.0 * self.edge                                         # exact in float32: the frame keeps it as it is
             self.widenings += 1
         self.pairs = total
         self.keys = torch.empty((0,), dtype=torch.int64, device=dev)
@@ -225,18 +218,13 @@ def point_mesh_distances(points, vertices, faces, max_dist=20.0, return_face=Fal
         face = torch.full((nq,), -1, dtype=torch.int32, device=dev)
         box = _mesh_box(vertices) if nq and Nf and Nv else None
         if box is not None:
-            report = {"queries": nq, "faces": Nf, "budget": pair_budget(Nf), "second_pass_queries": 0}
-            fine = _FaceGrid(vertices, faces32, box[0], box[1], cap / FINE_CELLS_PER_MAX_DIST)
+            fine, coarse, unfinished = evaluation._two_pass_search(
+                points, cap, lambda edge: _FaceGrid(vertices, faces32, box[0], box[1], edge), _first_pass, _second_pass,
+                dist, face)
+            report = {"queries": nq, "faces": Nf, "budget": pair_budget(Nf), "second_pass_queries": unfinished}
             report.update(fine.report("fine_"))
-            if fine.pairs:                                                 # no pair: no face has a surface
-                done = torch.empty((nq,), dtype=torch.uint8, device=dev)
-                _first_pass(points, fine, cap, dist, face, done)
-                todo = torch.nonzero(done == 0).view(-1)                   # plumbing: the list of unfinished queries
-                report["second_pass_queries"] = int(todo.numel())
-                if report["second_pass_queries"]:
-                    coarse = _FaceGrid(vertices, faces32, box[0], box[1], cap * MARGIN)
-                    report.update(coarse.report("coarse_"))
-                    _second_pass(points, todo, coarse, cap, dist, face)
+            if coarse is not None:
+                report.update(coarse.report("coarse_"))
             _last_report = report
     return (dist, face.long()) if return_face else dist
 
@@ -246,16 +234,6 @@ def _sample(vertices, faces, pitch, seed):
         mesh_ops._check_sampling("sample_surface", pitch, seed)
         return torch.zeros((0, 3), dtype=torch.float32, device=vertices.device)
     return mesh_ops.sample_surface(vertices, faces, pitch, seed)[0]
-
-
-def _scores(d_acc, acc_used, d_comp, comp_used, counts):
-    acc_mean, acc_median = evaluation._mean_median(d_acc[acc_used])
-    comp_mean, comp_median = evaluation._mean_median(d_comp[comp_used])
-    out = {"accuracy_mean": acc_mean, "accuracy_median": acc_median, "completeness_mean": comp_mean,
-           "completeness_median": comp_median, "overall": (acc_mean + comp_mean) / 2.0}
-    out.update(counts)
-    out.update(n_data_used=int(acc_used.sum()), n_gt_used=int(comp_used.sum()))
-    return out
 
 
 def evaluate_mesh(vertices, faces, gt, pitch=0.2, max_dist=20.0, obs_mask=None, bb_min=None, res=None, plane=None, seed=0,
@@ -275,17 +253,10 @@ def evaluate_mesh(vertices, faces, gt, pitch=0.2, max_dist=20.0, obs_mask=None, 
     samples = _sample(vertices, faces, pitch, seed)
     d_acc = evaluation.nearest_distances(samples, gt, max_dist)
     d_comp = point_mesh_distances(gt, vertices, faces, max_dist)
-    acc_used = d_acc < cap
-    if obs_mask is not None:
-        acc_used &= evaluation.in_obs_mask(samples, obs_mask, bb_min, res)
-    comp_used = d_comp < cap
-    if plane is not None:
-        comp_used &= evaluation.above_plane(gt, plane)
     n = int(samples.shape[0])
-    out = _scores(d_acc, acc_used, d_comp, comp_used, {"n_data": n, "n_data_thinned": n, "n_gt": int(gt.shape[0]), "n_samples": n})
-    if return_distances:
-        out.update(samples=samples, d_acc=d_acc, d_comp=d_comp, acc_used=acc_used, comp_used=comp_used)
-    return out
+    return evaluation._scores(d_acc, samples, d_comp, gt, cap,
+                              {"n_data": n, "n_data_thinned": n, "n_gt": int(gt.shape[0]), "n_samples": n},
+                              {"samples": samples} if return_distances else None, obs_mask, bb_min, res, plane)
 
 
 def evaluate_point_cloud_on_mesh(data, gt_vertices, gt_faces, gt_pitch=0.2, min_dist=0.2, max_dist=20.0, obs_mask=None,
@@ -306,18 +277,11 @@ def evaluate_point_cloud_on_mesh(data, gt_vertices, gt_faces, gt_pitch=0.2, min_
     samples = _sample(gt_vertices, gt_faces, gt_pitch, seed)
     d_acc = point_mesh_distances(thinned, gt_vertices, gt_faces, max_dist)
     d_comp = evaluation.nearest_distances(samples, thinned, max_dist)
-    acc_used = d_acc < cap
-    if obs_mask is not None:
-        acc_used &= evaluation.in_obs_mask(thinned, obs_mask, bb_min, res)
-    comp_used = d_comp < cap
-    if plane is not None:
-        comp_used &= evaluation.above_plane(samples, plane)
     n = int(samples.shape[0])
-    out = _scores(d_acc, acc_used, d_comp, comp_used, {"n_data": int(data.shape[0]), "n_data_thinned": int(thinned.shape[0]),
-                                                        "n_gt": n, "n_samples": n})
-    if return_distances:
-        out.update(data_thinned=thinned, samples=samples, d_acc=d_acc, d_comp=d_comp, acc_used=acc_used, comp_used=comp_used)
-    return out
+    counts = {"n_data": int(data.shape[0]), "n_data_thinned": int(thinned.shape[0]), "n_gt": n, "n_samples": n}
+    return evaluation._scores(d_acc, thinned, d_comp, samples, cap, counts,
+                              {"data_thinned": thinned, "samples": samples} if return_distances else None,
+                              obs_mask, bb_min, res, plane)
 
 
 def load_ply_surface(path, dev):
@@ -329,17 +293,6 @@ def load_ply_surface(path, dev):
             torch.from_numpy(np.ascontiguousarray(faces).astype(np.int64)).to(dev))
 
 
-def _dtu_filters(obs_mask_mat, plane_mat):
-    from .utils import io as IO
-    kw = {}
-    if obs_mask_mat is not None:
-        mask, bb_min, res = IO.load_dtu_obs_mask(obs_mask_mat)
-        kw.update(obs_mask=mask, bb_min=bb_min, res=res)
-    if plane_mat is not None:
-        kw.update(plane=IO.load_dtu_plane(plane_mat))
-    return kw
-
-
 def evaluate_mesh_ply(data_ply, gt_ply, obs_mask_mat=None, plane_mat=None, pitch=0.2, max_dist=20.0, seed=0, device=None,
                       return_distances=False):
     """``evaluate_mesh`` of a PLY with faces (``utils.io.load_ply_mesh``) against the vertices of a ground-truth PLY, with
@@ -349,7 +302,7 @@ def evaluate_mesh_ply(data_ply, gt_ply, obs_mask_mat=None, plane_mat=None, pitch
     vertices, faces = load_ply_surface(data_ply, dev)
     gt = torch.from_numpy(IO.load_ply_points(gt_ply)).to(dev)
     return evaluate_mesh(vertices, faces, gt, pitch=pitch, max_dist=max_dist, seed=seed, return_distances=return_distances,
-                         **_dtu_filters(obs_mask_mat, plane_mat))
+                         **evaluation._dtu_filters(obs_mask_mat, plane_mat))
 
 
 def evaluate_ply_on_mesh(data_ply, gt_mesh_ply, obs_mask_mat=None, plane_mat=None, gt_pitch=0.2, min_dist=0.2, max_dist=20.0,
@@ -361,4 +314,4 @@ def evaluate_ply_on_mesh(data_ply, gt_mesh_ply, obs_mask_mat=None, plane_mat=Non
     gt_vertices, gt_faces = load_ply_surface(gt_mesh_ply, dev)
     return evaluate_point_cloud_on_mesh(data, gt_vertices, gt_faces, gt_pitch=gt_pitch, min_dist=min_dist, max_dist=max_dist,
                                         thin=thin, seed=seed, return_distances=return_distances,
-                                        **_dtu_filters(obs_mask_mat, plane_mat))
+                                        **evaluation._dtu_filters(obs_mask_mat, plane_mat))
