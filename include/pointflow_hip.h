@@ -817,6 +817,49 @@ int pf_tsdf_emit_triangles(const float* tsdf, const int* weight, int nx, int ny,
 int pf_tsdf_vertices_f32(const int64_t* keys, int64_t count, const float* tsdf, const unsigned char* colour, float ox, float oy,
                          float oz, float voxel, int nx, int ny, int nz, float* vertices, unsigned char* colours, void* stream);
 
+/* ---- sparse TSDF volumes: brick allocation, integration, marching tetrahedra (csrc/sparse_tsdf.hip) ---------------------
+ * The volume of the pf_tsdf_* block stored only near the surface (specification: pointmvsnet_amd/sparse_tsdf.py).  The
+ * virtual grid has nx x ny x nz samples, at most PF_SPARSE_TSDF_MAX_AXIS per axis; a brick holds 8 x 8 x 8 of them, brick
+ * (bi, bj, bk) = (i >> 3, j >> 3, k >> 3) has the key (bk NBy + bj) NBx + bi with NB* = ceil(n* / 8), and NBx NBy NBz < 2^31.
+ * keys (bricks,) int64 are the allocated bricks, sorted and unique, bricks * 512 <= INT32_MAX; row b of S, W (bricks, 512), CS
+ * (bricks, 512, 3) and CW belongs to keys[b], local index (lk * 8 + lj) * 8 + li.  proj, depths, images as for
+ * pf_tsdf_integrate_f32.
+ * pf_sparse_tsdf_touch: touched (NBx NBy NBz) uint8, one byte per virtual brick, set to 1 (never cleared, so calls
+ *   accumulate) where some view passes the brick test: the brick's box grown by one sample per side is projected by its 8
+ *   corners (qx, qy, z as in pf_tsdf_integrate_f32); m = 2^-20 (max |p8 X| + |p9 Y| + |p10 Z| + |p11| + trunc); the view is
+ *   skipped if zhi + m <= depth_min or zlo - m >= depth_max; the pixel box is the whole image unless zlo - m > depth_min and
+ *   2^-20 (max(|qx| terms, |qy| terms) + max(w, h) max |z| terms) < zlo / 4, else the corners' floor(u), floor(v) bounding
+ *   box padded by one pixel and clipped; the brick is touched if a pixel of the box has depth_min < d < depth_max and
+ *   (zlo - trunc) - m <= d <= (zhi + trunc) + m.  A NaN among the projections: the whole image and every valid d.
+ * pf_sparse_tsdf_neighbours: rows (bricks, 7) int32: the rows of the +x, +y, +xy, +z, +xz, +yz, +xyz bricks of each brick
+ *   (column c - 1 for c = dx + 2 dy + 4 dz), -1 where that brick is outside the grid or not among keys.
+ * pf_sparse_tsdf_integrate_f32: pf_tsdf_integrate_f32 on the samples of the allocated bricks that lie inside the grid; the
+ *   others are not touched.
+ * pf_sparse_tsdf_count_triangles: count (bricks, 512) int32 per cell, owned by the brick of its corner 0, as
+ *   pf_tsdf_count_triangles; a corner in a brick that is not allocated counts as weight 0; min_weight >= 1.  tsdf and weight
+ *   are (bricks, 512).
+ * pf_sparse_tsdf_emit_triangles: as pf_tsdf_emit_triangles in the order of count; the keys are those of the virtual grid,
+ *   ((k ny + j) nx + i) * 8 + direction bits.
+ * pf_sparse_tsdf_vertices_f32: as pf_tsdf_vertices_f32 for keys of the virtual grid, tsdf (bricks, 512) and colour
+ *   (bricks, 512, 3) uint8; a key with an end in a brick that is not allocated gives (0, 0, 0) as well. */
+#define PF_SPARSE_TSDF_MAX_AXIS 1048576
+int pf_sparse_tsdf_touch(const float* depths, const float* proj, int V, int h, int w, float ox, float oy, float oz, float voxel,
+                         int nx, int ny, int nz, float trunc, float depth_min, float depth_max, unsigned char* touched,
+                         void* stream);
+int pf_sparse_tsdf_neighbours(const int64_t* keys, int64_t bricks, int nx, int ny, int nz, int* rows, void* stream);
+int pf_sparse_tsdf_integrate_f32(const int64_t* keys, int64_t bricks, const float* depths, const unsigned char* images,
+                                 const float* proj, int V, int h, int w, float ox, float oy, float oz, float voxel, int nx, int ny,
+                                 int nz, float trunc, float depth_min, float depth_max, float* S, int* W, int* CS, int* CW,
+                                 void* stream);
+int pf_sparse_tsdf_count_triangles(const float* tsdf, const int* weight, const int* rows, int64_t bricks, int min_weight,
+                                   int* count, void* stream);
+int pf_sparse_tsdf_emit_triangles(const int64_t* keys, int64_t bricks, const float* tsdf, const int* weight, const int* rows,
+                                  int nx, int ny, int nz, int min_weight, const int64_t* inclusive, int64_t faces,
+                                  int64_t* tri_keys, void* stream);
+int pf_sparse_tsdf_vertices_f32(const int64_t* edge_keys, int64_t count, const int64_t* keys, int64_t bricks, const float* tsdf,
+                                const unsigned char* colour, float ox, float oy, float oz, float voxel, int nx, int ny, int nz,
+                                float* vertices, unsigned char* colours, void* stream);
+
 /* ---- mesh clean-up and scoring: components, vertex normals, surface samples (csrc/mesh_ops.hip) -----------------------
  * The specification is this project's own (pointmvsnet_amd/mesh_ops.py).  vertices (Nv, 3) float32, faces (Nf, 3) int32,
  * Nv, Nf <= PF_MESH_OPS_MAX.  Every kernel skips a face with an index outside [0, Nv); no argument can make one fault.

@@ -145,6 +145,13 @@ PROTOTYPES = {
     "pf_tsdf_count_triangles": ([_vp, _vp, _i, _i, _i, _i, _vp, _vp], _i),
     "pf_tsdf_emit_triangles": ([_vp, _vp, _i, _i, _i, _i, _vp, _i64, _vp, _vp], _i),
     "pf_tsdf_vertices_f32": ([_vp, _i64, _vp, _vp, _f, _f, _f, _f, _i, _i, _i, _vp, _vp, _vp], _i),
+    "pf_sparse_tsdf_touch": ([_vp, _vp, _i, _i, _i, _f, _f, _f, _f, _i, _i, _i, _f, _f, _f, _vp, _vp], _i),
+    "pf_sparse_tsdf_neighbours": ([_vp, _i64, _i, _i, _i, _vp, _vp], _i),
+    "pf_sparse_tsdf_integrate_f32": ([_vp, _i64, _vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _f, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp,
+                                      _vp, _vp], _i),
+    "pf_sparse_tsdf_count_triangles": ([_vp, _vp, _vp, _i64, _i, _vp, _vp], _i),
+    "pf_sparse_tsdf_emit_triangles": ([_vp, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i64, _vp, _vp], _i),
+    "pf_sparse_tsdf_vertices_f32": ([_vp, _i64, _vp, _i64, _vp, _vp, _f, _f, _f, _f, _i, _i, _i, _vp, _vp, _vp], _i),
     "pf_mesh_cc_hook": ([_vp, _i64, _i64, _vp, _vp, _vp], _i),
     "pf_mesh_cc_compress": ([_vp, _i64, _vp], _i),
     "pf_mesh_face_labels": ([_vp, _i64, _i64, _vp, _vp, _vp], _i),

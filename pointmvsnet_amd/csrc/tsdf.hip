@@ -19,17 +19,15 @@
 //                   function of (tetrahedron, case) and nothing else.
 //   tsdf_vertices   one thread per unique key: the vertex from the key alone, so every cell that refers to it sees one value.
 //
-// The tetrahedra are (0, r[t], r[t + 1], 7) with r = 1 3 2 6 4 5 1: the ring is packed into one integer, the inside and
-// outside corners of a tetrahedron into 3-bit fields of two more.  No table in memory, no per-thread array, no scratch, no
-// LDS.  Any two corners of such a tetrahedron are comparable as bit sets, so the lower end of an edge is the smaller corner
-// number and its direction bits are the exclusive or of the two.
+// The update of a sample by a view, the tetrahedron ring, the triangles of a cell, the edge keys and the vertex arithmetic are
+// those of pf_tsdf.h, shared with the sparse volume (sparse_tsdf.hip).  No table in memory, no per-thread array, no scratch, no
+// LDS.
 #include "pf_common.h"
+#include "pf_tsdf.h"
 
 #include <math.h>
 
 namespace {
-
-constexpr unsigned kTsdfRing = 1u | (3u << 3) | (2u << 6) | (6u << 9) | (4u << 12) | (5u << 15) | (1u << 18);
 
 __global__ __launch_bounds__(256) void tsdf_integrate_kernel(const float* __restrict__ depths,
                                                              const unsigned char* __restrict__ images,
@@ -46,44 +44,24 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(const float* __rest
   const float X = ox + (float)i * voxel, Y = oy + (float)j * voxel, Z = oz + (float)k * voxel;
   const float wf = (float)w, hf = (float)h;
   const int64_t hw = (int64_t)h * w;
-  float s = S[n];
-  int cnt = W[n];
-  int cr = 0, cg = 0, cb = 0, cw = 0;
+  TsdfSums a = {S[n], W[n], 0, 0, 0, 0};
   if (images != nullptr) {
-    cr = CS[(int64_t)n * 3 + 0];
-    cg = CS[(int64_t)n * 3 + 1];
-    cb = CS[(int64_t)n * 3 + 2];
-    cw = CW[n];
+    a.cr = CS[(int64_t)n * 3 + 0];
+    a.cg = CS[(int64_t)n * 3 + 1];
+    a.cb = CS[(int64_t)n * 3 + 2];
+    a.cw = CW[n];
   }
   for (int view = 0; view < V; ++view) {
     const float* __restrict__ p = proj + (int64_t)view * PF_RENDER_PROJ_FLOATS;      // wave-uniform: scalar loads
-    const float qx = ((p[0] * X + p[1] * Y) + p[2] * Z) + p[3];
-    const float qy = ((p[4] * X + p[5] * Y) + p[6] * Z) + p[7];
-    const float z = ((p[8] * X + p[9] * Y) + p[10] * Z) + p[11];
-    if (!(z > depth_min && z < depth_max)) continue;                               // false for NaN
-    const float u = qx / z, v = qy / z;
-    if (!(u >= 0.0f && u < wf && v >= 0.0f && v < hf)) continue;                   // as floats: the conversions are in range
-    const int64_t pix = (int64_t)view * hw + ((int64_t)(int)floorf(v) * w + (int)floorf(u));
-    const float d = depths[pix];
-    if (!(d > depth_min && d < depth_max)) continue;
-    const float sdf = d - z;
-    if (sdf < -trunc) continue;                                                    // behind the surface
-    s += fminf(sdf, trunc) / trunc;
-    cnt += 1;
-    if (images != nullptr && fabsf(sdf) <= trunc) {
-      cr += (int)images[pix * 3 + 0];
-      cg += (int)images[pix * 3 + 1];
-      cb += (int)images[pix * 3 + 2];
-      cw += 1;
-    }
+    tsdf_integrate_view(p, depths, images, view, hw, w, wf, hf, X, Y, Z, trunc, depth_min, depth_max, a);
   }
-  S[n] = s;
-  W[n] = cnt;
+  S[n] = a.s;
+  W[n] = a.cnt;
   if (images != nullptr) {
-    CS[(int64_t)n * 3 + 0] = cr;
-    CS[(int64_t)n * 3 + 1] = cg;
-    CS[(int64_t)n * 3 + 2] = cb;
-    CW[n] = cw;
+    CS[(int64_t)n * 3 + 0] = a.cr;
+    CS[(int64_t)n * 3 + 1] = a.cg;
+    CS[(int64_t)n * 3 + 2] = a.cb;
+    CW[n] = a.cw;
   }
 }
 
@@ -103,49 +81,6 @@ __device__ __forceinline__ int tsdf_cell_mask(const float* __restrict__ tsdf, co
   return active ? mask : -1;
 }
 
-// the corners of tetrahedron t in its listed order, 3 bits each
-__device__ __forceinline__ unsigned tsdf_tet(int t) {
-  return ((kTsdfRing >> (3 * t)) & 63u) << 3 | (7u << 9);
-}
-
-__device__ __forceinline__ int tsdf_tet_triangles(unsigned tet, int mask) {
-  int inside = 0;
-#pragma unroll
-  for (int c = 0; c < 4; ++c) inside += (mask >> ((tet >> (3 * c)) & 7u)) & 1;
-  return inside == 2 ? 2 : (inside == 1 || inside == 3 ? 1 : 0);
-}
-
-__device__ __forceinline__ int tsdf_cx(unsigned c) { return (int)(c & 1u); }
-__device__ __forceinline__ int tsdf_cy(unsigned c) { return (int)((c >> 1) & 1u); }
-__device__ __forceinline__ int tsdf_cz(unsigned c) { return (int)(c >> 2); }
-
-// the key of the edge between corners p and q of the cell whose corner 0 is sample `base`
-__device__ __forceinline__ int64_t tsdf_edge_key(unsigned p, unsigned q, int base, int nx, int nxy) {
-  const unsigned lo = p < q ? p : q;
-  return (int64_t)(base + tsdf_cx(lo) + tsdf_cy(lo) * nx + tsdf_cz(lo) * nxy) * 8 + (int64_t)(p ^ q);
-}
-
-// One triangle on the edges (p0, q0) (p1, q1) (p2, q2); sp, sq: the coordinate sums of the tetrahedron's inside and outside
-// corners packed as x | y << 4 | z << 8, np of them inside.  Writes three keys, the last two swapped unless the right-hand
-// normal of the triangle through the edge midpoints has a positive dot product with mean(Q) - mean(P).
-__device__ __forceinline__ void tsdf_put_triangle(unsigned p0, unsigned q0, unsigned p1, unsigned q1, unsigned p2, unsigned q2,
-                                                  int np, int sp, int sq, int base, int nx, int nxy, int64_t* __restrict__ out) {
-  const int m0x = tsdf_cx(p0) + tsdf_cx(q0), m0y = tsdf_cy(p0) + tsdf_cy(q0), m0z = tsdf_cz(p0) + tsdf_cz(q0);
-  const int ax = tsdf_cx(p1) + tsdf_cx(q1) - m0x, ay = tsdf_cy(p1) + tsdf_cy(q1) - m0y, az = tsdf_cz(p1) + tsdf_cz(q1) - m0z;
-  const int bx = tsdf_cx(p2) + tsdf_cx(q2) - m0x, by = tsdf_cy(p2) + tsdf_cy(q2) - m0y, bz = tsdf_cz(p2) + tsdf_cz(q2) - m0z;
-  const int nq = 4 - np;
-  const int dx = np * (sq & 15) - nq * (sp & 15);                      // |P| |Q| (mean(Q) - mean(P))
-  const int dy = np * ((sq >> 4) & 15) - nq * ((sp >> 4) & 15);
-  const int dz = np * (sq >> 8) - nq * (sp >> 8);
-  const int dot = (ay * bz - az * by) * dx + (az * bx - ax * bz) * dy + (ax * by - ay * bx) * dz;
-  const int64_t k0 = tsdf_edge_key(p0, q0, base, nx, nxy);
-  const int64_t k1 = tsdf_edge_key(p1, q1, base, nx, nxy);
-  const int64_t k2 = tsdf_edge_key(p2, q2, base, nx, nxy);
-  out[0] = k0;
-  out[1] = dot > 0 ? k1 : k2;
-  out[2] = dot > 0 ? k2 : k1;
-}
-
 // the linear sample index of corner 0 of cell (k (ny - 1) + j) (nx - 1) + i
 __device__ __forceinline__ int tsdf_cell_base(int cell, int nx, int ny) {
   const int cx = nx - 1, cy = ny - 1;
@@ -160,12 +95,7 @@ __global__ __launch_bounds__(256) void tsdf_count_kernel(const float* __restrict
   if (c64 >= cells) return;
   const int base = tsdf_cell_base((int)c64, nx, ny);
   const int mask = tsdf_cell_mask(tsdf, weight, base, nx, nx * ny, min_weight);
-  int triangles = 0;
-  if (mask > 0 && mask < 255) {
-#pragma unroll
-    for (int t = 0; t < 6; ++t) triangles += tsdf_tet_triangles(tsdf_tet(t), mask);
-  }
-  count[c64] = triangles;
+  count[c64] = tsdf_cell_triangles(mask);
 }
 
 __global__ __launch_bounds__(256) void tsdf_emit_kernel(const float* __restrict__ tsdf, const int* __restrict__ weight, int nx,
@@ -177,41 +107,7 @@ __global__ __launch_bounds__(256) void tsdf_emit_kernel(const float* __restrict_
   const int base = tsdf_cell_base((int)c64, nx, ny);
   const int mask = tsdf_cell_mask(tsdf, weight, base, nx, nxy, min_weight);
   if (!(mask > 0 && mask < 255)) return;
-  int64_t at = c64 ? incl[c64 - 1] : 0;
-  for (int t = 0; t < 6; ++t) {
-    const unsigned tet = tsdf_tet(t);
-    unsigned P = 0, Q = 0;                                              // corners in listed order, 3 bits each
-    int np = 0, nq = 0, sp = 0, sq = 0;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const unsigned corner = (tet >> (3 * c)) & 7u;
-      const int packed = tsdf_cx(corner) | (tsdf_cy(corner) << 4) | (tsdf_cz(corner) << 8);
-      if ((mask >> corner) & 1) {
-        P |= corner << (3 * np);
-        ++np;
-        sp += packed;
-      } else {
-        Q |= corner << (3 * nq);
-        ++nq;
-        sq += packed;
-      }
-    }
-    if (np == 0 || np == 4) continue;
-    const int triangles = np == 2 ? 2 : 1;
-    if (at + triangles > faces) return;                                 // a prefix sum that is not this volume's: write nothing
-    const unsigned P0 = P & 7u, P1 = (P >> 3) & 7u, P2 = (P >> 6) & 7u;
-    const unsigned Q0 = Q & 7u, Q1 = (Q >> 3) & 7u, Q2 = (Q >> 6) & 7u;
-    int64_t* out = keys + at * 3;
-    if (np == 1) {
-      tsdf_put_triangle(P0, Q0, P0, Q1, P0, Q2, np, sp, sq, base, nx, nxy, out);
-    } else if (np == 3) {
-      tsdf_put_triangle(P0, Q0, P1, Q0, P2, Q0, np, sp, sq, base, nx, nxy, out);
-    } else {
-      tsdf_put_triangle(P0, Q0, P0, Q1, P1, Q1, np, sp, sq, base, nx, nxy, out);
-      tsdf_put_triangle(P0, Q0, P1, Q1, P1, Q0, np, sp, sq, base, nx, nxy, out + 3);
-    }
-    at += triangles;
-  }
+  tsdf_emit_cell<int>(mask, base, nx, nxy, c64 ? incl[c64 - 1] : 0, faces, keys);
 }
 
 __global__ __launch_bounds__(256) void tsdf_vertices_kernel(const int64_t* __restrict__ keys, int64_t count,
@@ -225,7 +121,7 @@ __global__ __launch_bounds__(256) void tsdf_vertices_kernel(const int64_t* __res
   const int dir = (int)(key & 7);
   const int64_t a64 = key >> 3;
   const int64_t total = (int64_t)nx * ny * nz;
-  float px = 0.0f, py = 0.0f, pz = 0.0f;
+  bool edge = false;
   int r = 0, g = 0, b = 0;
   if (a64 >= 0 && a64 < total) {
     const int a = (int)a64;
@@ -233,29 +129,19 @@ __global__ __launch_bounds__(256) void tsdf_vertices_kernel(const int64_t* __res
     const int j = jk % ny, k = jk / ny;
     const int dx = dir & 1, dy = (dir >> 1) & 1, dz = dir >> 2;
     if (dir != 0 && i + dx < nx && j + dy < ny && k + dz < nz) {       // a key that is not this volume's reads nothing
+      edge = true;
       const int bb = a + dx + dy * nx + dz * nx * ny;
-      const float fa = tsdf[a], fb = tsdf[bb];
-      const float t = fa / (fa - fb);
-      const float ax = ox + (float)i * voxel, ay = oy + (float)j * voxel, az = oz + (float)k * voxel;
-      const float bx = ox + (float)(i + dx) * voxel, by = oy + (float)(j + dy) * voxel, bz = oz + (float)(k + dz) * voxel;
-      px = ax + t * (bx - ax);
-      py = ay + t * (by - ay);
-      pz = az + t * (bz - az);
+      const float t = tsdf_vertex(tsdf[a], tsdf[bb], i, j, k, dx, dy, dz, ox, oy, oz, voxel, vertices + n * 3);
       if (colour != nullptr) {
         const unsigned char* ca = colour + (int64_t)a * 3;
         const unsigned char* cb = colour + (int64_t)bb * 3;
-        const float fr = floorf(((float)ca[0] + t * ((float)cb[0] - (float)ca[0])) + 0.5f);
-        const float fg = floorf(((float)ca[1] + t * ((float)cb[1] - (float)ca[1])) + 0.5f);
-        const float fbl = floorf(((float)ca[2] + t * ((float)cb[2] - (float)ca[2])) + 0.5f);
-        r = (int)fminf(fmaxf(fr, 0.0f), 255.0f);                       // (fmaxf(NaN, 0) = 0: the conversion is in range)
-        g = (int)fminf(fmaxf(fg, 0.0f), 255.0f);
-        b = (int)fminf(fmaxf(fbl, 0.0f), 255.0f);
+        r = tsdf_vertex_colour(ca[0], cb[0], t);
+        g = tsdf_vertex_colour(ca[1], cb[1], t);
+        b = tsdf_vertex_colour(ca[2], cb[2], t);
       }
     }
   }
-  vertices[n * 3 + 0] = px;
-  vertices[n * 3 + 1] = py;
-  vertices[n * 3 + 2] = pz;
+  if (!edge) vertices[n * 3 + 0] = vertices[n * 3 + 1] = vertices[n * 3 + 2] = 0.0f;
   if (colours != nullptr) {
     colours[n * 3 + 0] = (unsigned char)r;
     colours[n * 3 + 1] = (unsigned char)g;

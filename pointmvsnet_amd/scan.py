@@ -49,6 +49,7 @@ from .normals import depth_normals
 from .photometric import photometric_consistency, photometric_filter
 from .refine import scale_of, upsample_depth_maps, upsampled_intrinsics
 from .render import depth_map_errors, render_depth_maps, render_mesh_depth_maps
+from .sparse_tsdf import MAX_VIRTUAL_SAMPLES, SparseTSDFVolume
 from .tsdf import TSDFVolume, dims_for, volume_bounds
 from .utils.eval_file_logger import _resize_nearest, _scene_paths
 from .utils.io import write_ply
@@ -205,6 +206,7 @@ class ScanAccumulator(object):
         self.last_clean_report = None
         self.last_photo_report = None
         self.last_mesh_report = None
+        self.last_sparse_report = None
         self._with_image = 0
         self._K = np.zeros((self.view_num, 3, 3))
         self._E = np.zeros((self.view_num, 4, 4))
@@ -436,12 +438,15 @@ class ScanAccumulator(object):
         return render_mesh_depth_maps(vertices, faces, K, E, int(self._depth.shape[1]), int(self._depth.shape[2]), **kwargs)
 
     def mesh(self, voxel, trunc=None, min_weight=2, bounds=None, filtered=True, with_colour=True,
-             min_component_faces=None, keep_largest=None, with_normals=False):
+             min_component_faces=None, keep_largest=None, with_normals=False, sparse=False):
         """``(vertices (Nv, 3) float32, faces (Nf, 3) int32, colours (Nv, 3) uint8 or None)``: the accumulated depth maps --
         ``filtered()``, or the raw ``predictions()[0]`` with ``filtered=False`` -- integrated into a ``tsdf.TSDFVolume`` of
         pitch ``voxel`` and truncation ``trunc`` (default ``4 * voxel``) over the box ``bounds = (lo, hi)`` (default:
         ``tsdf.volume_bounds`` of the maps used, grown by ``trunc``), and its zero surface through the cells whose corners
-        were all seen by ``min_weight`` views (``tsdf.extract_mesh``).  Colours need the views' images.
+        were all seen by ``min_weight`` views (``tsdf.extract_mesh``).  Colours need the views' images.  With ``sparse`` the
+        same call goes through a ``sparse_tsdf.SparseTSDFVolume`` (the same vertices and colours byte for byte and the same
+        faces in another order; ``min_weight >= 1``; the grid may then have more than 2^31 samples), whose ``report()`` is
+        kept as ``last_sparse_report`` (None after a dense call).
 
         ``min_component_faces`` and ``keep_largest`` drop the mesh's small connected components
         (``mesh_ops.remove_small_components``: ``min_faces``, ``keep_largest``); the report -- ``components``,
@@ -456,11 +461,13 @@ class ScanAccumulator(object):
         depths = self.filtered() if filtered else self._depth
         if bounds is None:
             bounds = volume_bounds(depths, K, E, pad=trunc)
-        origin, dims = dims_for(bounds, voxel)
+        origin, dims = dims_for(bounds, voxel, max_samples=MAX_VIRTUAL_SAMPLES if sparse else None)
         images = self.images() if with_colour else None
-        volume = TSDFVolume(origin, voxel, dims, trunc, with_colour=images is not None, device=depths.device)
+        volume = (SparseTSDFVolume if sparse else TSDFVolume)(origin, voxel, dims, trunc, with_colour=images is not None,
+                                                              device=depths.device)
         volume.integrate(depths, K, E, images=images)
         vertices, faces, colours = volume.extract(min_weight)[:3]
+        self.last_sparse_report = volume.report() if sparse else None
         self.last_mesh_report = None
         if min_component_faces is not None or keep_largest is not None:
             Nv, Nf = int(vertices.shape[0]), int(faces.shape[0])

@@ -76,7 +76,8 @@ kernel over the keys.
 
 Out of scope
 ------------
-Sparse or hashed volumes; per-axis voxel sizes; weighting by angle or confidence; de-integration; trilinear depth
+Hashed volumes (a volume stored only near the surface, in bricks found by binary search, is ``sparse_tsdf.py``: the same
+specification and, for ``min_weight >= 1``, the same mesh byte for byte); per-axis voxel sizes; weighting by angle or confidence; de-integration; trilinear depth
 sampling; vertex normals from the TSDF gradient; mesh simplification or smoothing; Poisson reconstruction.  (Looking at
 the mesh from a camera is ``render.render_mesh_depth_maps``; dropping its small components, area-weighted vertex normals
 and samples of its surface are ``mesh_ops.py``.)
@@ -94,8 +95,9 @@ MAX_SAMPLES = 2 ** 31 - 1                      # PF_TSDF_MAX_SAMPLES of include/
 MAX_VIEWS, MAX_VIEWS_COLOUR = 2 ** 31 - 1, (2 ** 31 - 1) // 255
 
 
-def _check_grid(who, origin, voxel, dims):
-    """``((ox, oy, oz), voxel, (nx, ny, nz))`` as Python numbers, or the ValueError of ``who``."""
+def _check_grid(who, origin, voxel, dims, max_samples=MAX_SAMPLES):
+    """``((ox, oy, oz), voxel, (nx, ny, nz))`` as Python numbers, or the ValueError of ``who``.  ``max_samples`` is the dense
+    volume's limit unless the caller states another (``sparse_tsdf.py``: its grid is virtual)."""
     try:
         origin = tuple(float(o) for o in np.asarray(cm.host_f64(origin)).reshape(-1))
         dims_f = tuple(float(d) for d in np.asarray(dims).reshape(-1))
@@ -106,8 +108,9 @@ def _check_grid(who, origin, voxel, dims):
     if len(dims_f) != 3 or any(d != int(d) or d < 1 for d in dims_f):
         raise ValueError("%s: dims must be three integers (nx, ny, nz) of at least 1" % who)
     dims = tuple(int(d) for d in dims_f)
-    if dims[0] * dims[1] * dims[2] > MAX_SAMPLES:
-        raise ValueError("%s: %d x %d x %d samples; a volume has fewer than 2^31" % ((who,) + dims))
+    if dims[0] * dims[1] * dims[2] > max_samples:
+        raise ValueError("%s: %d x %d x %d samples; a volume has fewer than 2^%d" %
+                         ((who,) + dims + ((max_samples + 1).bit_length() - 1,)))
     voxel = float(voxel)
     if not (voxel > 0.0 and math.isfinite(voxel)):
         raise ValueError("%s: voxel must be a positive length" % who)
@@ -282,9 +285,10 @@ def volume_bounds(depths, intrinsics, extrinsics, depth_min=1e-3, depth_max=1e5,
     return lo.double().cpu().numpy() - float(pad), hi.double().cpu().numpy() + float(pad)
 
 
-def dims_for(bounds, voxel):
+def dims_for(bounds, voxel, max_samples=None):
     """``(origin (3,) float64, dims (nx, ny, nz))`` of the smallest volume of pitch ``voxel`` whose samples span the box
-    ``bounds = (lo, hi)``: ``origin = lo`` and ``n = ceil((hi - lo) / voxel) + 1`` per axis."""
+    ``bounds = (lo, hi)``: ``origin = lo`` and ``n = ceil((hi - lo) / voxel) + 1`` per axis.  ``max_samples``: the dense
+    volume's limit unless the caller states another (a sparse volume's grid is virtual)."""
     lo, hi = (np.asarray(cm.host_f64(b), dtype=np.float64).reshape(-1) for b in bounds)
     voxel = float(voxel)
     if lo.shape != (3,) or hi.shape != (3,) or not (np.isfinite(lo).all() and np.isfinite(hi).all() and (hi >= lo).all()):
@@ -292,6 +296,7 @@ def dims_for(bounds, voxel):
     if not (voxel > 0.0 and math.isfinite(voxel)):
         raise ValueError("dims_for: voxel must be a positive length")
     dims = tuple(int(n) for n in np.ceil((hi - lo) / voxel).astype(np.int64) + 1)
-    if dims[0] * dims[1] * dims[2] > MAX_SAMPLES:
-        raise ValueError("dims_for: %d x %d x %d samples; a volume has fewer than 2^31" % dims)
+    if dims[0] * dims[1] * dims[2] > (MAX_SAMPLES if max_samples is None else max_samples):
+        raise ValueError("dims_for: %d x %d x %d samples; a volume has fewer than 2^%d" %
+                         (dims + (31 if max_samples is None else (max_samples + 1).bit_length() - 1,)))
     return lo.copy(), dims

@@ -5,7 +5,7 @@ preprocessing, the network, the batched confidence filter, the fusion and, optio
         [--mode LANCZOS4] [--init-prob-threshold 0.2] [--flow-prob-threshold 0.1] [--name flow2] \
         [--fusion roundtrip --num-src 10 --save-depth DIR] [--normals [--normal-step 2]] \
         [--voxel 0.2] [--outlier-radius 2.0 [--outlier-k 16] [--outlier-std 2.0] [--min-neighbors 4]] \
-        [--mesh mesh.ply --mesh-voxel 0.5 [--mesh-trunc 2.0] [--mesh-min-weight 2] [--save-mesh-depth DIR]] \
+        [--mesh mesh.ply --mesh-voxel 0.5 [--mesh-trunc 2.0] [--mesh-min-weight 2] [--mesh-sparse] [--save-mesh-depth DIR]] \
         [--mesh-min-component 100] [--mesh-keep-largest 1] [--mesh-normals] [--mesh-sample-pitch 0.2] \
         [--gt stl009_total.ply --obs-mask ObsMask9_10.mat --plane Plane9.mat [--depth-errors --splat 1]] \
         [--gt-mesh surface.ply --depth-errors] \
@@ -35,7 +35,9 @@ With ``--mesh`` the filtered depth maps are also integrated into a TSDF volume o
 with faces (pointmvsnet_amd/tsdf.py); the JSON line then carries ``mesh``: the grid size, the vertex and face counts and, with
 ``--gt``, ``evaluate_point_cloud`` of the mesh's vertices as ``score``, next to the cloud's.  ``--save-mesh-depth DIR`` also
 rasterises that mesh back into the scan's own views (``ScanAccumulator.render_mesh``) and writes every view's fused,
-hole-filled depth map as ``%08d_mesh.pfm``.
+hole-filled depth map as ``%08d_mesh.pfm``.  ``--mesh-sparse`` integrates into a sparse volume instead
+(pointmvsnet_amd/sparse_tsdf.py: the same mesh, the state only near the surface, grids beyond 2^31 samples); ``mesh`` then
+carries ``sparse``: the virtual and the allocated bricks and the state's bytes next to the dense volume's.
 ``--mesh-min-component N`` and ``--mesh-keep-largest K`` drop the mesh's connected components of fewer than ``N`` faces and
 all but the ``K`` largest before it is written (pointmvsnet_amd/mesh_ops.py); ``mesh`` then carries the ``components``
 report.  ``--mesh-normals`` writes area-weighted vertex normals, ``nx ny nz``, next to the faces.  With ``--gt``, ``mesh``
@@ -132,6 +134,8 @@ def main():
     ap.add_argument("--mesh-voxel", type=float, default=0.5, help="--mesh: the pitch of the TSDF volume")
     ap.add_argument("--mesh-trunc", type=float, default=None, help="--mesh: the truncation distance (default: 4 voxels)")
     ap.add_argument("--mesh-min-weight", type=int, default=2, help="--mesh: views that must have seen every corner of a cell")
+    ap.add_argument("--mesh-sparse", action="store_true",
+                    help="--mesh: integrate into a sparse volume of 8 x 8 x 8 bricks (pointmvsnet_amd/sparse_tsdf.py)")
     ap.add_argument("--save-mesh-depth", default=None, help="--mesh: folder for every view's depth map of the mesh, %%08d_mesh.pfm")
     ap.add_argument("--mesh-min-component", type=int, default=None, help="--mesh: drop components of fewer faces")
     ap.add_argument("--mesh-keep-largest", type=int, default=None, help="--mesh: keep only this many components, the largest")
@@ -254,7 +258,10 @@ def main():
         mesh_kwargs = {"voxel": args.mesh_voxel, "trunc": args.mesh_trunc, "min_weight": args.mesh_min_weight}
         mesh_trunc = 4.0 * args.mesh_voxel if args.mesh_trunc is None else args.mesh_trunc
         K, E = acc.cameras()
-        _, dims = tsdf.dims_for(tsdf.volume_bounds(filtered, K, E, pad=mesh_trunc), args.mesh_voxel)   # the grid mesh() builds
+        _, dims = tsdf.dims_for(tsdf.volume_bounds(filtered, K, E, pad=mesh_trunc), args.mesh_voxel,   # the grid mesh() builds
+                                max_samples=2 ** 60 - 1 if args.mesh_sparse else None)
+        if args.mesh_sparse:
+            mesh_kwargs.update(sparse=True)
         if args.mesh_min_component is not None or args.mesh_keep_largest is not None:
             mesh_kwargs.update(min_component_faces=args.mesh_min_component, keep_largest=args.mesh_keep_largest)
         if args.mesh_normals:
@@ -264,6 +271,8 @@ def main():
                        "dims": list(dims), "vertices": int(mesh_vertices.shape[0]), "faces": int(faces.shape[0])}
         if acc.last_mesh_report is not None:
             out["mesh"]["components"] = acc.last_mesh_report
+        if acc.last_sparse_report is not None:
+            out["mesh"]["sparse"] = acc.last_sparse_report
         print("mesh: grid %d x %d x %d, %d vertices, %d faces" % (tuple(dims) + (out["mesh"]["vertices"], out["mesh"]["faces"])),
               file=sys.stderr)
         if args.save_mesh_depth:
