@@ -892,6 +892,40 @@ int pf_mesh_sample_count_f32(const float* vertices, int64_t Nv, const int* faces
 int pf_mesh_sample_emit_f32(const float* vertices, int64_t Nv, const int* faces, int64_t Nf, const int64_t* inclusive,
                             int64_t N, unsigned seed, float* points, int* face_index, float* bary, void* stream);
 
+/* ---- mesh simplification: vertex clustering with quadric placement (csrc/mesh_simplify.hip) ---------------------------
+ * The specification is this project's own (pointmvsnet_amd/mesh_simplify.py).  vertices (Nv, 3) float32, faces (Nf, 3) int32,
+ * Nv, Nf <= PF_MESH_OPS_MAX; cluster (Nv) int64 is pf_cloud_voxel_reduce_f32's inverse map onto M <= Nv clusters.  No
+ * argument can make a kernel fault: every index is checked where it is read.
+ * pf_mesh_simplify_faces: triple (Nf, 3) int32 = (cluster[a], cluster[b], cluster[c]) in the face's own order, ascending
+ *   (Nf, 3) int32 the same three numbers sorted, collapsed (Nf) = 1 iff two of them are equal; a face with an index outside
+ *   [0, Nv) or a cluster outside [0, M) gets (-1, -1, -1) and collapsed = 1.
+ * pf_mesh_simplify_keep_first: sorted_faces (K) int64 are face indices ordered by their ascending triple (by a stable sort,
+ *   so ascending inside a run of equal triples); keep[sorted_faces[t]] = 1 iff t = 0 or the triple differs from that of
+ *   sorted_faces[t - 1], else 0.  Other entries of keep (Nf) are not written.
+ * pf_mesh_quadric_thread_f64 / _wave_f64: offsets (M + 1) and corners (3 Nf) int64: cluster s owns the list
+ *   corners[offsets[s] .. offsets[s + 1]), corner 3 f + j being a corner of face f.  means (M, 3) float32.  In float64, per
+ *   list entry with its face (a, b, c): p' = p - mean per coordinate, e1 = p_b' - p_a', e2 = p_c' - p_a', n = e1 x e2 (each
+ *   component a product, a product, a difference), skipped unless finite; d = -((nx ax' + ny ay') + nz az'); the sums
+ *   A += n n^T (six entries) and b += d n.  t = (A00 + A11) + A22; unless t is finite and positive the position is the mean;
+ *   else lam = (regularisation * t) / 3, M = A + lam I is factored M = L D L^T (l10 = a01 / m00, l20 = a02 / m00,
+ *   d1 = m11 - l10 a01, u21 = a12 - l20 a01, l21 = u21 / d1, d2 = m22 - (l20 a02 + l21 u21)) and M x = -b solved (y0 = -b0,
+ *   y1 = -b1 - l10 y0, y2 = -b2 - (l20 y0 + l21 y1), x2 = y2 / d2, x1 = y1 / d1 - l21 x2, x0 = y0 / m00 - (l10 x1 + l20 x2));
+ *   if some |x_k| <= (double)cell does not hold, fallback[s] = 1 and x = 0.  positions (M, 3) = (float)(mean + x), fallback
+ *   (M) 0 / 1.  _thread: one thread per cluster, its list in ascending order; clusters whose list has `threshold` or more
+ *   entries are not written.  _wave: one wave per cluster todo[0 .. ntodo): lane l adds entries l, l + 64, .., the lanes'
+ *   sums are combined by the butterfly xor 32, 16, .. 1.  PF_MESH_SIMPLIFY_MIN_REG <= regularisation <= 1. */
+#define PF_MESH_SIMPLIFY_MIN_REG 1e-6
+int pf_mesh_simplify_faces(const int* faces, int64_t Nf, int64_t Nv, const int64_t* cluster, int64_t M, int* triple,
+                           int* ascending, unsigned char* collapsed, void* stream);
+int pf_mesh_simplify_keep_first(const int* ascending, int64_t Nf, const int64_t* sorted_faces, int64_t K,
+                                unsigned char* keep, void* stream);
+int pf_mesh_quadric_thread_f64(const float* vertices, int64_t Nv, const int* faces, int64_t Nf, const int64_t* offsets,
+                               const int64_t* corners, const float* means, int64_t M, float cell, double regularisation,
+                               int64_t threshold, float* positions, unsigned char* fallback, void* stream);
+int pf_mesh_quadric_wave_f64(const float* vertices, int64_t Nv, const int* faces, int64_t Nf, const int64_t* offsets,
+                             const int64_t* corners, const float* means, int64_t M, float cell, double regularisation,
+                             const int64_t* todo, int64_t ntodo, float* positions, unsigned char* fallback, void* stream);
+
 /* ---- exact point-to-mesh distances (csrc/mesh_distance.hip) -----------------------------------------------------------
  * The specification is this project's own (pointmvsnet_amd/mesh_distance.py): per query the lexicographic minimum of
  * (d2, face index) over the faces, d2 the squared distance to the triangle in float64 from the float32 coordinates.  The

@@ -158,6 +158,10 @@ PROTOTYPES = {
     "pf_mesh_vertex_normals_f32": ([_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp], _i),
     "pf_mesh_sample_count_f32": ([_vp, _i64, _vp, _i64, _f, ctypes.c_uint, _vp, _vp], _i),
     "pf_mesh_sample_emit_f32": ([_vp, _i64, _vp, _i64, _vp, _i64, ctypes.c_uint, _vp, _vp, _vp, _vp], _i),
+    "pf_mesh_simplify_faces": ([_vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp], _i),
+    "pf_mesh_simplify_keep_first": ([_vp, _i64, _vp, _i64, _vp, _vp], _i),
+    "pf_mesh_quadric_thread_f64": ([_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _f, _d, _i64, _vp, _vp, _vp], _i),
+    "pf_mesh_quadric_wave_f64": ([_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _f, _d, _vp, _i64, _vp, _vp, _vp], _i),
     "pf_mesh_dist_count_f32": ([_vp, _i64, _vp, _i64, _f, _f, _f, _f, _i, _i, _i, _i64, _vp, _vp], _i),
     "pf_mesh_dist_emit_f32": ([_vp, _i64, _vp, _i64, _f, _f, _f, _f, _i, _i, _i, _vp, _i64, _vp, _vp, _vp], _i),
     "pf_mesh_dist_pack_f32": ([_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp], _i),
@@ -337,6 +341,11 @@ _timer = None
 def set_timer(timer):
     global _timer
     _timer = timer
+
+
+def timing():
+    """Whether a ``KernelTimer`` is set: a caller whose ``algo_bytes`` cost a host read computes them only then."""
+    return _timer is not None
 
 
 _PROBE = set(filter(None, os.environ.get("PF_PROBE_DOUBLE", "").split(",")))   # sensitivity probe (tools only): run twice

@@ -18,7 +18,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "libpointflow_hip.so")
-SOURCES = ["pf_core.hip", "gather_knn.hip", "knn_lattice.hip", "fetch.hip", "edgeconv.hip", "norm.hip", "conv3d.hip", "conv3d_pair.hip", "deconv3d.hip", "conv3d_bottom.hip", "conv2d_wide.hip", "eval_out.hip", "knn_inverse.hip", "norm_bwd.hip", "conv_wgrad.hip", "conv_dgrad.hip", "warp_bwd.hip", "train_heads.hip", "fusion.hip", "preprocess.hip", "cloud_eval.hip", "scan_filter.hip", "geo_filter.hip", "cloud_render.hip", "depth_normals.hip", "depth_refine.hip", "depth_segments.hip", "photo_filter.hip", "cloud_filter.hip", "tsdf.hip", "sparse_tsdf.hip", "mesh_render.hip", "mesh_ops.hip", "mesh_distance.hip"]
+SOURCES = ["pf_core.hip", "gather_knn.hip", "knn_lattice.hip", "fetch.hip", "edgeconv.hip", "norm.hip", "conv3d.hip", "conv3d_pair.hip", "deconv3d.hip", "conv3d_bottom.hip", "conv2d_wide.hip", "eval_out.hip", "knn_inverse.hip", "norm_bwd.hip", "conv_wgrad.hip", "conv_dgrad.hip", "warp_bwd.hip", "train_heads.hip", "fusion.hip", "preprocess.hip", "cloud_eval.hip", "scan_filter.hip", "geo_filter.hip", "cloud_render.hip", "depth_normals.hip", "depth_refine.hip", "depth_segments.hip", "photo_filter.hip", "cloud_filter.hip", "tsdf.hip", "sparse_tsdf.hip", "mesh_render.hip", "mesh_ops.hip", "mesh_distance.hip", "mesh_simplify.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-munsafe-fp-atomics",
          "-fPIC", "-Wno-pass-failed", "-I" + INCLUDE, "-I" + CSRC]
 # every compile also reports the per-kernel resource usage; it is kept next to the object as JSON and merged into

@@ -147,16 +147,9 @@ def voxel_downsample(points, voxel, colors=None, normals=None, return_inverse=Fa
     n, dev = int(points.shape[0]), points.device
     colors = _check_attribute(colors, n, dev, torch.uint8, who, "colors")
     normals = _check_attribute(normals, n, dev, torch.float32, who, "normals")
-    inv = np.float32(1.0) / _radius(voxel, who, "voxel")
-    if not (np.isfinite(inv) and inv > 0.0):
-        raise ValueError("%s: voxel is too small" % who)
+    inv = _voxel_inverse(voxel, who, "voxel")
     if n:
-        lo = points.amin(dim=0).cpu().numpy()                              # plumbing: the bounding box, float32
-        hi = points.amax(dim=0).cpu().numpy()
-        top = np.floor((hi - lo) * inv)                                    # float32, monotone in p: the largest cell
-        if not np.isfinite(top).all() or float(top.max()) >= MAX_CELLS:
-            raise ValueError("%s: more than %d voxels on an axis" % (who, MAX_CELLS))
-        cells = [int(t) + 1 for t in top]
+        lo, cells = _voxel_cells(points, inv, who)
     _lib.require_gpu(points)
     with _lib.on_device(dev):
         if n == 0:
@@ -164,25 +157,58 @@ def voxel_downsample(points, voxel, colors=None, normals=None, return_inverse=Fa
             inverse = torch.zeros((0,), dtype=torch.int64, device=dev)
             counts = torch.zeros((0,), dtype=torch.int32, device=dev)
         else:
-            keys = torch.empty((n,), dtype=torch.int64, device=dev)
-            _lib.call("pf_cloud_voxel_keys_f32", _lib.ptr(points), n, *([float(v) for v in lo] + [float(inv)] + cells + [
-                _lib.ptr(keys), _lib.stream()]))
-            keys, order = torch.sort(keys, stable=True)                    # plumbing; stable: ascending index inside a voxel
-            first = torch.ones((n,), dtype=torch.bool, device=dev)
-            first[1:] = keys[1:] != keys[:-1]
-            starts = torch.nonzero(first).view(-1)                         # plumbing: the segment starts
-            m = int(starts.numel())
-            starts = torch.cat([starts, torch.full((1,), n, dtype=torch.int64, device=dev)])
-            out_points = torch.empty((m, 3), dtype=torch.float32, device=dev)
-            out_colors = None if colors is None else torch.empty((m, 3), dtype=torch.uint8, device=dev)
-            out_normals = None if normals is None else torch.empty((m, 3), dtype=torch.float32, device=dev)
-            counts = torch.empty((m,), dtype=torch.int32, device=dev)
-            inverse = torch.empty((n,), dtype=torch.int64, device=dev) if return_inverse else None
-            _lib.call("pf_cloud_voxel_reduce_f32", _lib.ptr(points), _lib.ptr(colors), _lib.ptr(normals), _lib.ptr(order),
-                      _lib.ptr(starts), n, m, _lib.ptr(out_points), _lib.ptr(out_colors), _lib.ptr(out_normals),
-                      _lib.ptr(counts), _lib.ptr(inverse), _lib.stream())
+            out_points, out_colors, out_normals, counts, inverse, _ = _voxel_reduce(points, lo, inv, cells, colors, normals,
+                                                                                    return_inverse)
             out = (out_points, out_colors, out_normals)
     return out + ((inverse,) if return_inverse else ()) + ((counts,) if return_counts else ())
+
+
+def _voxel_inverse(voxel, who, what):
+    """``float32(1) / float32(voxel)``, made on the host (module docstring, 4.)."""
+    inv = np.float32(1.0) / _radius(voxel, who, what)
+    if not (np.isfinite(inv) and inv > 0.0):
+        raise ValueError("%s: %s is too small" % (who, what))
+    return inv
+
+
+def _voxel_cells(points, inv, who, origin=None):
+    """``(o, cells per axis)`` of a non-empty cloud: ``o`` its per-axis float32 minimum, or ``origin`` (float32 (3,), which must
+    be ``<=`` that minimum on every axis); more than 2^17 cells on an axis is a ``ValueError``.  Two host reads."""
+    lo = points.amin(dim=0).cpu().numpy()                                  # plumbing: the bounding box, float32
+    hi = points.amax(dim=0).cpu().numpy()
+    if origin is not None:
+        if not (origin <= lo).all():
+            raise ValueError("%s: origin must be <= the smallest coordinate on every axis" % who)
+        lo = origin
+    top = np.floor((hi - lo) * inv)                                        # float32, monotone in p: the largest cell
+    if not np.isfinite(top).all() or float(top.max()) >= MAX_CELLS:
+        raise ValueError("%s: more than %d voxels on an axis" % (who, MAX_CELLS))
+    return lo, [int(t) + 1 for t in top]
+
+
+def _voxel_reduce(points, lo, inv, cells, colors, normals, want_inverse):
+    """The two kernels of the voxel merge on a non-empty cloud, on the current device: ``(points (M, 3), colors, normals,
+    counts (M,) int32, inverse (N,) int64 or None, (sorted keys (N,), segment starts (M + 1,)))``; rows come in ascending key.
+    ``mesh_simplify`` clusters a mesh's vertices with it."""
+    n, dev = int(points.shape[0]), points.device
+    keys = torch.empty((n,), dtype=torch.int64, device=dev)
+    _lib.call("pf_cloud_voxel_keys_f32", _lib.ptr(points), n, *([float(v) for v in lo] + [float(inv)] + cells + [
+        _lib.ptr(keys), _lib.stream()]))
+    keys, order = torch.sort(keys, stable=True)                            # plumbing; stable: ascending index inside a voxel
+    first = torch.ones((n,), dtype=torch.bool, device=dev)
+    first[1:] = keys[1:] != keys[:-1]
+    starts = torch.nonzero(first).view(-1)                                 # plumbing: the segment starts
+    m = int(starts.numel())
+    starts = torch.cat([starts, torch.full((1,), n, dtype=torch.int64, device=dev)])
+    out_points = torch.empty((m, 3), dtype=torch.float32, device=dev)
+    out_colors = None if colors is None else torch.empty((m, 3), dtype=torch.uint8, device=dev)
+    out_normals = None if normals is None else torch.empty((m, 3), dtype=torch.float32, device=dev)
+    counts = torch.empty((m,), dtype=torch.int32, device=dev)
+    inverse = torch.empty((n,), dtype=torch.int64, device=dev) if want_inverse else None
+    _lib.call("pf_cloud_voxel_reduce_f32", _lib.ptr(points), _lib.ptr(colors), _lib.ptr(normals), _lib.ptr(order),
+              _lib.ptr(starts), n, m, _lib.ptr(out_points), _lib.ptr(out_colors), _lib.ptr(out_normals),
+              _lib.ptr(counts), _lib.ptr(inverse), _lib.stream())
+    return out_points, out_colors, out_normals, counts, inverse, (keys, starts)
 
 
 def _select(keep, points, colors, normals):

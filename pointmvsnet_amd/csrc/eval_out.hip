@@ -93,9 +93,9 @@ int pf_eval_prob_filter_f32(const float* depth, const float* flow_conf, const fl
 // (geo_filter.hip), the point-cloud renderer (cloud_render.hip), the normal maps (depth_normals.hip), the guided depth
 // upsampling (depth_refine.hip), the depth maps' segments (depth_segments.hip), the photometric check (photo_filter.hip), the cloud cleaning
 // (cloud_filter.hip), the meshing (tsdf.hip, sparse_tsdf.hip), the mesh rasteriser (mesh_render.hip), the mesh clean-up (mesh_ops.hip) and the
-// point-to-mesh distances (mesh_distance.hip) with this unit, so that such a library exports the whole C ABI.  hipcc
+// point-to-mesh distances (mesh_distance.hip) and the mesh simplification (mesh_simplify.hip) with this unit, so that such a library exports the whole C ABI.  hipcc
 // compiles fusion.hip, preprocess.hip, cloud_eval.hip, scan_filter.hip, geo_filter.hip, cloud_render.hip,
-// depth_normals.hip, depth_refine.hip, depth_segments.hip, photo_filter.hip, cloud_filter.hip, tsdf.hip, sparse_tsdf.hip, mesh_render.hip, mesh_ops.hip and mesh_distance.hip as units of
+// depth_normals.hip, depth_refine.hip, depth_segments.hip, photo_filter.hip, cloud_filter.hip, tsdf.hip, sparse_tsdf.hip, mesh_render.hip, mesh_ops.hip, mesh_distance.hip and mesh_simplify.hip as units of
 // their own
 // (build.SOURCES) and never takes this branch.
 #if !defined(__HIP__)
@@ -115,4 +115,5 @@ int pf_eval_prob_filter_f32(const float* depth, const float* flow_conf, const fl
 #include "mesh_render.hip"
 #include "mesh_ops.hip"
 #include "mesh_distance.hip"
+#include "mesh_simplify.hip"
 #endif

@@ -78,9 +78,9 @@ bary.view(1, 1, -1, 3), faces, attributes)``.
 
 Out of scope
 ------------
-Smoothing; simplification or decimation; hole filling; non-manifold repair; edge-connectivity (as opposed to
+Smoothing; edge-collapse decimation; hole filling; non-manifold repair; edge-connectivity (as opposed to
 vertex-connectivity) components; area thresholds for components; a wave-shared path for hub vertices.  (Point-to-triangle
-distances are pointmvsnet_amd/mesh_distance.py.)
+distances are pointmvsnet_amd/mesh_distance.py; simplification by vertex clustering is pointmvsnet_amd/mesh_simplify.py.)
 """
 import math
 

@@ -40,7 +40,7 @@ so its results differ from this statement in the last bits; a zero weight times 
 import numpy as np
 import torch
 
-from . import _lib, mesh_ops
+from . import _lib, mesh_ops, mesh_simplify
 from .cloud_filter import clean_cloud
 from .depth_segments import check_clean_settings, clean_depth_maps
 from .fusion import fuse_depth_maps
@@ -206,6 +206,7 @@ class ScanAccumulator(object):
         self.last_clean_report = None
         self.last_photo_report = None
         self.last_mesh_report = None
+        self.last_simplify_report = None
         self.last_sparse_report = None
         self._with_image = 0
         self._K = np.zeros((self.view_num, 3, 3))
@@ -438,7 +439,8 @@ class ScanAccumulator(object):
         return render_mesh_depth_maps(vertices, faces, K, E, int(self._depth.shape[1]), int(self._depth.shape[2]), **kwargs)
 
     def mesh(self, voxel, trunc=None, min_weight=2, bounds=None, filtered=True, with_colour=True,
-             min_component_faces=None, keep_largest=None, with_normals=False, sparse=False):
+             min_component_faces=None, keep_largest=None, with_normals=False, sparse=False, simplify_cell=None,
+             simplify_placement="quadric"):
         """``(vertices (Nv, 3) float32, faces (Nf, 3) int32, colours (Nv, 3) uint8 or None)``: the accumulated depth maps --
         ``filtered()``, or the raw ``predictions()[0]`` with ``filtered=False`` -- integrated into a ``tsdf.TSDFVolume`` of
         pitch ``voxel`` and truncation ``trunc`` (default ``4 * voxel``) over the box ``bounds = (lo, hi)`` (default:
@@ -451,9 +453,16 @@ class ScanAccumulator(object):
         ``min_component_faces`` and ``keep_largest`` drop the mesh's small connected components
         (``mesh_ops.remove_small_components``: ``min_faces``, ``keep_largest``); the report -- ``components``,
         ``vertices_before`` / ``_after``, ``faces_before`` / ``_after``, ``rounds`` -- is kept as ``last_mesh_report`` (None
-        after a call with neither).  With ``with_normals`` a fourth value, the vertex normals (Nv, 3) float32 of the mesh
-        that is returned (``mesh_ops.vertex_normals``)."""
+        after a call with neither).  With ``simplify_cell`` the mesh that is left is simplified by vertex clustering on a grid
+        of that edge (``mesh_simplify.simplify_mesh`` with ``placement=simplify_placement``), after the small pieces have
+        gone, so that floaters add no quadrics; its report is kept as ``last_simplify_report`` (None after a call without).
+        With ``with_normals`` a fourth value, the vertex normals (Nv, 3) float32 of the mesh that is returned
+        (``mesh_ops.vertex_normals``)."""
         mesh_ops._check_selection("ScanAccumulator.mesh", min_component_faces, keep_largest)
+        if simplify_cell is not None:
+            mesh_simplify.check_simplify_arguments("ScanAccumulator.mesh", simplify_cell, simplify_placement)
+        elif simplify_placement not in mesh_simplify.PLACEMENTS:
+            raise ValueError("ScanAccumulator.mesh: placement must be one of %s" % ", ".join(mesh_simplify.PLACEMENTS))
         self._require_complete("mesh")
         voxel = float(voxel)
         trunc = 4.0 * voxel if trunc is None else float(trunc)
@@ -479,6 +488,10 @@ class ScanAccumulator(object):
                 vertices, faces, colours = mesh_ops._compact(vertices, faces, face_keep, colours, None)[:3]
             self.last_mesh_report = {"components": components, "vertices_before": Nv, "vertices_after": int(vertices.shape[0]),
                                      "faces_before": Nf, "faces_after": int(faces.shape[0]), "rounds": rounds}
+        self.last_simplify_report = None
+        if simplify_cell is not None:
+            vertices, faces, colours, self.last_simplify_report = mesh_simplify.simplify_mesh(
+                vertices, faces, simplify_cell, colours=colours, placement=simplify_placement)
         if with_normals:
             return vertices, faces, colours, mesh_ops.vertex_normals(vertices, faces)
         return vertices, faces, colours

@@ -78,9 +78,9 @@ Out of scope
 ------------
 Hashed volumes (a volume stored only near the surface, in bricks found by binary search, is ``sparse_tsdf.py``: the same
 specification and, for ``min_weight >= 1``, the same mesh byte for byte); per-axis voxel sizes; weighting by angle or confidence; de-integration; trilinear depth
-sampling; vertex normals from the TSDF gradient; mesh simplification or smoothing; Poisson reconstruction.  (Looking at
+sampling; vertex normals from the TSDF gradient; mesh smoothing; Poisson reconstruction.  (Looking at
 the mesh from a camera is ``render.render_mesh_depth_maps``; dropping its small components, area-weighted vertex normals
-and samples of its surface are ``mesh_ops.py``.)
+and samples of its surface are ``mesh_ops.py``; simplifying it is ``mesh_simplify.py``.)
 """
 import math
 

@@ -7,6 +7,7 @@ preprocessing, the network, the batched confidence filter, the fusion and, optio
         [--voxel 0.2] [--outlier-radius 2.0 [--outlier-k 16] [--outlier-std 2.0] [--min-neighbors 4]] \
         [--mesh mesh.ply --mesh-voxel 0.5 [--mesh-trunc 2.0] [--mesh-min-weight 2] [--mesh-sparse] [--save-mesh-depth DIR]] \
         [--mesh-min-component 100] [--mesh-keep-largest 1] [--mesh-normals] [--mesh-sample-pitch 0.2] \
+        [--mesh-simplify 2.0 [--mesh-simplify-placement mean]] \
         [--gt stl009_total.ply --obs-mask ObsMask9_10.mat --plane Plane9.mat [--depth-errors --splat 1]] \
         [--gt-mesh surface.ply --depth-errors] \
         [--photo-ncc 0.6 [--photo-radius 2 --photo-min-consistent 2 --photo-min-variance 25]] \
@@ -43,6 +44,10 @@ all but the ``K`` largest before it is written (pointmvsnet_amd/mesh_ops.py); ``
 report.  ``--mesh-normals`` writes area-weighted vertex normals, ``nx ny nz``, next to the faces.  With ``--gt``, ``mesh``
 also gains ``score_sampled``: ``evaluate_point_cloud`` of ``sample_surface`` of the written mesh at ``--mesh-sample-pitch``
 (default: the evaluation's ``min_dist``), next to the unchanged ``score`` of its vertices, whose density is the voxel's.
+``--mesh-simplify CELL`` simplifies the mesh that is left (after the small components have gone, before the normals) by
+vertex clustering on a grid of edge ``CELL`` with quadric placement (pointmvsnet_amd/mesh_simplify.py; ``mean`` with
+``--mesh-simplify-placement``); ``mesh`` then carries ``simplify``: the report and the boundary / manifold / non-manifold edge
+counts before and after, and with ``--gt`` also ``score_surface_before_simplification``.
 With ``--gt-mesh FILE`` (a PLY with faces) ``--depth-errors`` scores against the rasterised surface instead of the splatted
 cloud: no holes, and no back of the scene seen through a nearer surface; ``--splat`` is then not used.  The line's
 ``ground_truth`` names which of the two was used, ``"mesh"`` or ``"cloud"``.
@@ -140,6 +145,10 @@ def main():
     ap.add_argument("--mesh-min-component", type=int, default=None, help="--mesh: drop components of fewer faces")
     ap.add_argument("--mesh-keep-largest", type=int, default=None, help="--mesh: keep only this many components, the largest")
     ap.add_argument("--mesh-normals", action="store_true", help="--mesh: write area-weighted vertex normals")
+    ap.add_argument("--mesh-simplify", type=float, default=None, metavar="CELL",
+                    help="--mesh: simplify the mesh by vertex clustering on a grid of this edge (pointmvsnet_amd/mesh_simplify.py)")
+    ap.add_argument("--mesh-simplify-placement", default="quadric", choices=["quadric", "mean"],
+                    help="--mesh-simplify: where a cluster's vertex goes")
     ap.add_argument("--mesh-sample-pitch", type=float, default=None,
                     help="--mesh with --gt: the pitch of the surface samples that are scored (default: the evaluation's min_dist)")
     ap.add_argument("--name", default="flow2")
@@ -266,13 +275,31 @@ def main():
             mesh_kwargs.update(min_component_faces=args.mesh_min_component, keep_largest=args.mesh_keep_largest)
         if args.mesh_normals:
             mesh_kwargs.update(with_normals=True)
-        mesh_vertices, faces = acc.write_mesh(args.mesh, **mesh_kwargs)[:2]
+        unsimplified = None
+        if args.mesh_simplify is not None:                       # one integration: the mesh as extracted, then its simplification
+            from pointmvsnet_amd import mesh_ops, mesh_simplify
+            mesh_simplify.check_simplify_arguments("--mesh-simplify", args.mesh_simplify, args.mesh_simplify_placement)
+            unsimplified = acc.mesh(**dict(mesh_kwargs, with_normals=False))
+            mesh_vertices, faces, mesh_colours, simplify_report = mesh_simplify.simplify_mesh(
+                unsimplified[0], unsimplified[1], args.mesh_simplify, colours=unsimplified[2],
+                placement=args.mesh_simplify_placement)
+            mesh_normals = mesh_ops.vertex_normals(mesh_vertices, faces) if args.mesh_normals else None
+            io.write_ply(args.mesh, mesh_vertices.cpu().numpy(), None if mesh_colours is None else mesh_colours.cpu().numpy(),
+                         None if mesh_normals is None else mesh_normals.cpu().numpy(), faces=faces.cpu().numpy())
+        else:
+            mesh_vertices, faces = acc.write_mesh(args.mesh, **mesh_kwargs)[:2]
         out["mesh"] = {"out": args.mesh, "voxel": args.mesh_voxel, "trunc": mesh_trunc, "min_weight": args.mesh_min_weight,
                        "dims": list(dims), "vertices": int(mesh_vertices.shape[0]), "faces": int(faces.shape[0])}
         if acc.last_mesh_report is not None:
             out["mesh"]["components"] = acc.last_mesh_report
         if acc.last_sparse_report is not None:
             out["mesh"]["sparse"] = acc.last_sparse_report
+        if unsimplified is not None:
+            out["mesh"]["simplify"] = dict(simplify_report, cell=args.mesh_simplify, placement=args.mesh_simplify_placement,
+                                           edges_before=mesh_simplify.mesh_edge_counts(unsimplified[1]),
+                                           edges_after=mesh_simplify.mesh_edge_counts(faces))
+            print("simplified at cell %g (%s): %s" % (args.mesh_simplify, args.mesh_simplify_placement,
+                                                      json.dumps(out["mesh"]["simplify"])), file=sys.stderr)
         print("mesh: grid %d x %d x %d, %d vertices, %d faces" % (tuple(dims) + (out["mesh"]["vertices"], out["mesh"]["faces"])),
               file=sys.stderr)
         if args.save_mesh_depth:
@@ -330,6 +357,9 @@ def main():
                 out["mesh"]["score_sampled"] = evaluation.evaluate_point_cloud(samples, gt, **kw)
             from pointmvsnet_amd import mesh_distance
             out["mesh"]["score_surface"] = mesh_distance.evaluate_mesh(mesh_vertices, faces, gt, pitch=pitch, **kw)
+            if unsimplified is not None and unsimplified[1].shape[0]:
+                out["mesh"]["score_surface_before_simplification"] = mesh_distance.evaluate_mesh(
+                    unsimplified[0], unsimplified[1], gt, pitch=pitch, **kw)
     if args.gt_mesh and points.shape[0]:
         from pointmvsnet_amd import mesh_distance
         kw = {}
